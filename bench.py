@@ -16,7 +16,13 @@ cpu_baseline: the CPU oracle (kind "port" — the reference Go/AVX2 path
 cannot run here, no Go toolchain) timed on host cores over
 a bounded sample.
 
+A plain run does only what the headline figure needs: stage, warm up, time
+the steps, optionally dump the outputs, print the result line.  --full adds
+the roofline split (extra timed launches) and the CPU baseline; without it
+those two fields of the result line are null.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--op encode|decode]
+                       [--full] [--dump-outputs DIR]
 """
 import argparse
 import ctypes
@@ -51,6 +57,41 @@ def log(msg):
         print(msg, file=sys.stderr, flush=True)
 
 
+# --dump-outputs: device bytes copied back per output array; stored as
+# float32 (4 B/value), so the arrays stay well under 64 MB in all
+DUMP_BUDGET = 8 << 20
+DUMP_CHUNK = 4096
+
+
+def dump_rows(lib, ctx, check, base, nrows, row_off, valid, packed=False):
+    """Copy back an output laid out as nrows rows of `valid` bytes, row r at
+    base + row_off(r), as a float32 array.  Everything when it fits
+    DUMP_BUDGET, else a fixed seeded sample of DUMP_CHUNK-byte pieces.
+    packed: the rows lie back to back, so everything is one copy."""
+    import numpy as np
+    vp = ctypes.c_void_p
+    if nrows * valid <= DUMP_BUDGET:
+        if packed:
+            pieces = [(0, 0, nrows * valid)]
+        else:
+            pieces = [(r, 0, valid) for r in range(nrows)]
+    else:
+        ch = min(DUMP_CHUNK, valid)
+        k = DUMP_BUDGET // ch
+        rng = np.random.RandomState(SEED & 0xFFFFFFFF)
+        rows = rng.randint(0, nrows, size=k)
+        offs = rng.randint(0, valid - ch + 1, size=k)
+        pieces = [(int(r), int(o), ch) for r, o in zip(rows, offs)]
+    out = np.empty(sum(ln for _, _, ln in pieces), dtype=np.uint8)
+    buf = ctypes.create_string_buffer(max(ln for _, _, ln in pieces))
+    pos = 0
+    for r, o, ln in pieces:
+        check(lib.mec_memcpy_d2h(ctx, buf, vp(base + row_off(r) + o), ln))
+        out[pos:pos + ln] = np.frombuffer(buf, dtype=np.uint8, count=ln)
+        pos += ln
+    return out.astype(np.float32)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -61,7 +102,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=6)
     ap.add_argument("--op", default="encode", choices=list(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="override batch/GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline split and the CPU "
+                         "baseline (extra runs; off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as "
+                         "DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     import minio_amd
@@ -240,9 +288,36 @@ def main():
     input_bytes_per_step = n * bs * world
     gib = input_bytes_per_step * args.steps / max_wall / (1 << 30)
 
+    # ---- outputs of the last timed step (before anything reruns) ----
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = "" if world == 1 else f".rank{rank}"
+        arrays = {}
+        if is_decode:
+            # the caller receives the erased rows of every item, rebuilt
+            # in place: rows 0..n_er-1 of each total-row item
+            arrays["reconstructed"] = dump_rows(
+                lib, ctx, check, dev_shards.value, n * n_er,
+                lambda r: ((r // n_er) * total + r % n_er) * stride, S)
+        else:
+            last = (step_no[0] - 1) % 2 if use_pipe else 0
+            par = (dev_par, dev_par2)[last]
+            sm = (dev_sum, dev_sum2)[last]
+            arrays["parity"] = dump_rows(
+                lib, ctx, check, par.value, n * p,
+                lambda r: r * stride, S)
+            if algo:
+                arrays["sums"] = dump_rows(
+                    lib, ctx, check, sm.value, n * total,
+                    lambda r: r * hsz, hsz, packed=True)
+        for name, arr in arrays.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}{sfx}.npy"), arr)
+        log(f"[bench] dumped {', '.join(arrays)} to {args.dump_outputs}")
+
     # ---- roofline: dominant-kernel split via HIP events (rank 0, N==1) ----
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # encode-only leg (GF kernel alone) vs fused to split GF vs hash
         k = max(4, args.steps // 2)
         def timed(fn):
@@ -299,7 +374,7 @@ def main():
 
     # ---- CPU baseline: oracle timed on host cores (bounded sample) ----
     cpu_baseline = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         lib_o = oracle._lib
         cores = os.cpu_count() or 1
         sample_n = 1024  # blocks; tens of CPU-core-seconds at 1 MiB blocks
