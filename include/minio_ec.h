@@ -157,6 +157,56 @@ mec_status mec_reconstruct_batch_dev_async(mec_ctx *ctx, int n,
                                            const uint8_t *present,
                                            int64_t shard_len, int data_only);
 
+/* ---- batch reconstruct, one erasure pattern PER ITEM --------------------
+ *
+ * The calls above hold one pattern for the whole batch, which is one
+ * object's read.  A degraded read or heal batched ACROSS objects is not
+ * uniform: every object places its shards by its own rotation,
+ * Distribution = hashOrder(bucket/object, d+p)
+ * (cmd/erasure-metadata-utils.go:178, applied to the drive list by
+ * shuffleDisks, cmd/erasure-metadata-utils.go:323), so one dead drive is a different missing logical row in each object, and
+ * a bitrot hit (cmd/bitrot-streaming.go:185-197) changes the pattern of a
+ * single block.  Here present + i*(d+p) is item i's own mask; the shim
+ * fills it per block from the rows it could read and verify
+ * (INTEGRATION.md "Shard distribution").
+ *
+ * Layout and in-place semantics are mec_reconstruct_batch_dev's:
+ * n * (d+p) * stride bytes, missing rows rebuilt in their slots from the
+ * item's first d present rows (data rows only when data_only); present
+ * rows are never written.  Per item:
+ *   - nothing to rebuild (all rows present, or data_only with all data
+ *     rows present): skipped;
+ *   - fewer than d rows present: unrecoverable.  With item_status non-NULL
+ *     item_status[i] = MEC_ERR_TOO_FEW_SHARDS, the item's bytes are left
+ *     untouched, every other item is rebuilt with item_status MEC_OK and
+ *     the call returns MEC_OK — one unreadable object does not fail the
+ *     batch.  With item_status NULL the call returns
+ *     MEC_ERR_TOO_FEW_SHARDS before anything is launched or modified.
+ * One matrix inversion per DISTINCT mask per call, and one kernel launch
+ * per rebuilt-row count in use (at most 8 per call while no pattern
+ * rebuilds more than 8 rows), whatever the number of patterns.  n is not
+ * limited to 65535.
+ * _async does not synchronize the stream (pair with mec_stream_sync);
+ * back-to-back _async calls with different masks need no sync in between.
+ * The host-pointer variant takes packed n*(d+p)*shard_len bytes, uploads
+ * them in one plain unchunked copy (no overlapped ingest yet), and writes
+ * back only the rebuilt rows. */
+mec_status mec_reconstruct_batch_mixed_dev(mec_ctx *ctx, int n,
+                                           void *shards_dev,
+                                           const uint8_t *present,
+                                           int64_t shard_len, int data_only,
+                                           uint8_t *item_status);
+mec_status mec_reconstruct_batch_mixed_dev_async(mec_ctx *ctx, int n,
+                                                 void *shards_dev,
+                                                 const uint8_t *present,
+                                                 int64_t shard_len,
+                                                 int data_only,
+                                                 uint8_t *item_status);
+mec_status mec_reconstruct_batch_mixed(mec_ctx *ctx, int n, uint8_t *shards,
+                                       const uint8_t *present,
+                                       int64_t shard_len, int data_only,
+                                       uint8_t *item_status);
+
 /* ---- batch bitrot hash / verify ----------------------------------------
  * msgs: n messages of msg_len bytes at msg_stride; sums: n * hash_size.
  * verify: ok_out[i]=1 where digest matches want[i] (errFileCorrupt map). */

@@ -15,6 +15,11 @@ surfaces 1:1 for tests and benchmarks:
                             (cmd/erasure-encode.go:76, erasure-decode.go:239,
                              :317) over the streaming bitrot on-disk layout
                             (cmd/bitrot-streaming.go)
+  - Erasure.reconstruct_batch
+                        <-> DecodeDataBlocks / DecodeDataAndParityBlocks
+                            for many blocks in one call, each with its own
+                            erasure pattern (a cross-object degraded read
+                            or heal; mec_reconstruct_batch_mixed)
   - bitrot_verify       <-> bitrotVerify (cmd/bitrot.go:164-216)
 
 No CPU fallback exists: constructing an Erasure on a machine without a
@@ -97,7 +102,10 @@ def _load():
     lib.mec_reconstruct_batch.argtypes = [vp, i32, u8p, u8p, i64, i32]
     lib.mec_reconstruct_batch_dev.argtypes = [vp, i32, vp, u8p, i64, i32]
     lib.mec_reconstruct_batch_dev_async.argtypes = [vp, i32, vp, u8p, i64, i32]
-    lib.mec_bitrot_sum_batch.argtypes = [vp, i32, i32, u8p, i64, i64, u8p]
+    lib.mec_reconstruct_batch_mixed.argtypes = [vp, i32, u8p, u8p, i64, i32, u8p]
+    lib.mec_reconstruct_batch_mixed_dev.argtypes = [vp, i32, vp, u8p, i64, i32, u8p]
+    lib.mec_reconstruct_batch_mixed_dev_async.argtypes = [vp, i32, vp, u8p, i64, i32, u8p]
+    lib.mec_bitrot_sum_batch.argtypes =[vp, i32, i32, u8p, i64, i64, u8p]
     lib.mec_bitrot_sum_batch_dev.argtypes = [vp, i32, i32, vp, i64, i64, vp]
     lib.mec_bitrot_verify_batch.argtypes = [vp, i32, i32, u8p, i64, i64, u8p, u8p]
     lib.mec_bitrot_verify_stream.argtypes = [vp, u8p, i64, i64, i32, u8p, i64]
@@ -277,6 +285,54 @@ class Erasure:
             else:
                 out.append(shards[i])
         return out
+
+    def reconstruct_batch(self, items, data_only=False):
+        """Reconstruct many blocks in one call, each with its OWN erasure
+        pattern — what a degraded read or heal batched across objects
+        produces, since every object rotates its shards by hashOrder
+        (cmd/erasure-metadata-utils.go:178).
+
+        items: list of d+p-long lists of equal-length shards, None marking
+        a missing shard.  Returns (items_out, statuses): missing shards
+        filled in (data shards only when data_only; missing parity then
+        stays None), statuses[i] 0 or 3 (ErrTooFewShards).  An
+        unrecoverable item comes back unchanged with its status set; it
+        does not fail the rest of the batch."""
+        total = self.d + self.p
+        n = len(items)
+        if n == 0:
+            return [], []
+        for it in items:
+            assert len(it) == total
+        lens = {len(s) for it in items for s in it if s is not None}
+        if not lens:
+            return [list(it) for it in items], [3] * n
+        assert len(lens) == 1, "all shards of a batch share one length"
+        per = lens.pop()
+        present = bytes(0 if s is None else 1 for it in items for s in it)
+        hole = b"\0" * per
+        buf = ctypes.create_string_buffer(
+            b"".join(hole if s is None else s for it in items for s in it),
+            n * total * per)
+        status = ctypes.create_string_buffer(n)
+        _check(_lib.mec_reconstruct_batch_mixed(
+            self._ck(), n, buf, present, per, 1 if data_only else 0, status))
+        statuses = list(status.raw)
+        raw = buf.raw
+        out = []
+        for i, it in enumerate(items):
+            if statuses[i] != MEC_OK:
+                out.append(list(it))
+                continue
+            row = []
+            for s in range(total):
+                if it[s] is None and (s < self.d or not data_only):
+                    off = (i * total + s) * per
+                    row.append(raw[off:off + per])
+                else:
+                    row.append(it[s])
+            out.append(row)
+        return out, statuses
 
     # -- streaming-format drivers (Erasure.Encode / Decode / Heal) --
     def encode_stream(self, src: bytes, algo: int = HIGHWAYHASH256S):

@@ -15,6 +15,7 @@
 #include "../../include/minio_ec.h"
 #include "gf_host.h"
 #include "kernels.h"
+#include "recon_plan.h"
 
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -65,21 +66,11 @@ int hash_size(int algo) {
     }
 }
 
-/* 8x8 bit matrix of the GF(2^8)/0x11D linear map x -> c*x, packed as two
- * dwords (byte b = rowmask: bit a set iff output bit b depends on input
- * bit a) — the r2 bit-sliced matmul's runtime-matrix form (kernels.h). */
-void bs_pack_matrix(uint8_t c, uint32_t out[2]) {
-    uint64_t m = 0;
-    for (int b = 0; b < 8; b++) {
-        uint8_t row = 0;
-        for (int a = 0; a < 8; a++)
-            if ((mec::gf_mul(c, (uint8_t)(1u << a)) >> b) & 1)
-                row |= (uint8_t)(1u << a);
-        m |= (uint64_t)row << (8 * b);
-    }
-    out[0] = (uint32_t)m;
-    out[1] = (uint32_t)(m >> 32);
-}
+using mec::bs_pack_matrix; /* recon_plan.cpp */
+
+static_assert(mec::kPlanMaxD == MEC_KMAX_D && mec::kPlanMaxE == MEC_KMAX_E &&
+                  mec::kPlanMaxTotal == MEC_KMAX_TOTAL,
+              "recon_plan.h caps must mirror kernels.h");
 
 } // namespace
 
@@ -109,6 +100,20 @@ struct mec_ctx {
     size_t cap_a = 0, cap_b = 0, cap_c = 0, cap_d = 0, cap_m = 0;
     void *pin = nullptr;
     size_t cap_pin = 0;
+
+    /* mixed-pattern reconstruct: the plan table + work lists of one call
+     * live in dev_x; they get there by a stream-ordered copy from one of
+     * two pinned staging slots, so back-to-back async calls never drain
+     * the stream.  ev_x[s] marks slot s's copy done (the slot may then be
+     * refilled); dev_x itself is only rewritten behind the kernels that
+     * read it, by stream order. */
+    void *dev_x = nullptr;
+    size_t cap_x = 0;
+    void *pin_x[2] = {nullptr, nullptr};
+    size_t cap_pin_x[2] = {0, 0};
+    hipEvent_t ev_x[2] = {nullptr, nullptr};
+    int x_idx = 0;
+    mec::ReconPlan plan; /* reused across calls to keep its allocations */
 
     mec_status ensure(void **buf, size_t *cap, size_t need) {
         if (*cap >= need) return MEC_OK;
@@ -291,6 +296,11 @@ void mec_ctx_destroy(mec_ctx *ctx) {
     if (ctx->dev_c) (void)hipFree(ctx->dev_c);
     if (ctx->dev_d) (void)hipFree(ctx->dev_d);
     if (ctx->dev_m) (void)hipFree(ctx->dev_m);
+    if (ctx->dev_x) (void)hipFree(ctx->dev_x);
+    for (int s = 0; s < 2; s++) {
+        if (ctx->pin_x[s]) (void)hipHostFree(ctx->pin_x[s]);
+        if (ctx->ev_x[s]) (void)hipEventDestroy(ctx->ev_x[s]);
+    }
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
@@ -748,6 +758,172 @@ mec_status mec_reconstruct_batch(mec_ctx *ctx, int n, uint8_t *shards,
                    pinb + ((size_t)b * total + s) * stride,
                    (size_t)shard_len);
         }
+    return MEC_OK;
+}
+
+/* ---- batch reconstruct, one erasure pattern per item ------------------- */
+
+/* Plans the call into ctx->plan.  With item_status NULL an unrecoverable
+ * item fails the whole call here, before anything is launched. */
+static mec_status mixed_plan_locked(mec_ctx *ctx, int n,
+                                    const uint8_t *present, int data_only,
+                                    uint8_t *item_status) {
+    if (!mec::build_reconstruct_plan(ctx->enc_matrix.data(), ctx->d, ctx->p,
+                                     n, present, data_only, &ctx->plan))
+        return MEC_ERR_INTERNAL;
+    if (ctx->plan.n_too_few && !item_status) return MEC_ERR_TOO_FEW_SHARDS;
+    if (item_status) memcpy(item_status, ctx->plan.status.data(), (size_t)n);
+    return MEC_OK;
+}
+
+/* Uploads ctx->plan and launches one kernel per output-row count in use.
+ * Never synchronizes the stream; the only host wait is on the copy that
+ * last read the pinned slot being refilled (two calls back). */
+static mec_status mixed_launch_locked(mec_ctx *ctx, void *shards_dev,
+                                      int64_t shard_len) {
+    const mec::ReconPlan &pl = ctx->plan;
+    if (pl.entries.empty()) return MEC_OK;
+    auto al16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t ent_bytes = pl.entries.size() * sizeof(mec::ReconPlanEntry);
+    const size_t mask_off = al16(ent_bytes);
+    const size_t mask_bytes = pl.masks.size() * sizeof(uint32_t);
+    size_t work_off[MEC_KMAX_E + 1];
+    size_t end = al16(mask_off + mask_bytes);
+    for (int e = 1; e <= MEC_KMAX_E; e++) {
+        work_off[e] = end;
+        end = al16(end + pl.work[e].size() * sizeof(mec::ReconWork));
+    }
+
+    const int slot = ctx->x_idx & 1;
+    ctx->x_idx ^= 1;
+    if (!ctx->ev_x[slot])
+        HIP_TRY(hipEventCreateWithFlags(&ctx->ev_x[slot],
+                                        hipEventDisableTiming));
+    else
+        HIP_TRY(hipEventSynchronize(ctx->ev_x[slot]));
+    if (ctx->cap_pin_x[slot] < end) {
+        if (ctx->pin_x[slot]) (void)hipHostFree(ctx->pin_x[slot]);
+        ctx->pin_x[slot] = nullptr;
+        ctx->cap_pin_x[slot] = 0;
+        HIP_TRY(hipHostMalloc(&ctx->pin_x[slot], end * 2));
+        ctx->cap_pin_x[slot] = end * 2;
+    }
+    /* growing dev_x frees the old buffer, which waits for the kernels
+     * still reading it; grow with slack so that stays rare */
+    if (ctx->cap_x < end) {
+        mec_status st = ctx->ensure(&ctx->dev_x, &ctx->cap_x, end * 2);
+        if (st != MEC_OK) return st;
+    }
+    uint8_t *pinb = (uint8_t *)ctx->pin_x[slot];
+    memcpy(pinb, pl.entries.data(), ent_bytes);
+    memcpy(pinb + mask_off, pl.masks.data(), mask_bytes);
+    for (int e = 1; e <= MEC_KMAX_E; e++)
+        if (!pl.work[e].empty())
+            memcpy(pinb + work_off[e], pl.work[e].data(),
+                   pl.work[e].size() * sizeof(mec::ReconWork));
+    HIP_TRY(hipMemcpyAsync(ctx->dev_x, pinb, end, hipMemcpyHostToDevice,
+                           ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_x[slot], ctx->stream));
+
+    const uint8_t *dx = (const uint8_t *)ctx->dev_x;
+    GfMixedArgs a{};
+    a.shards = (uint8_t *)shards_dev;
+    a.item_stride = (int64_t)(ctx->d + ctx->p) * ctx->stride;
+    a.row_stride = ctx->stride;
+    a.shard_len = shard_len;
+    a.entries = (const uint32_t *)dx;
+    a.masks = (const uint32_t *)(dx + mask_off);
+    a.d = ctx->d;
+    for (int e = 1; e <= MEC_KMAX_E; e++) {
+        if (pl.work[e].empty()) continue;
+        a.work = (const uint32_t *)(dx + work_off[e]);
+        a.n_work = (uint32_t)pl.work[e].size();
+        HIP_TRY(mec_launch_gf_matmul_mixed(&a, e, ctx->stream));
+    }
+    return MEC_OK;
+}
+
+static mec_status mixed_dev_locked(mec_ctx *ctx, int n, void *shards_dev,
+                                   const uint8_t *present, int64_t shard_len,
+                                   int data_only, uint8_t *item_status) {
+    if (n <= 0 || !shards_dev || !present || shard_len <= 0 ||
+        shard_len > ctx->stride)
+        return MEC_ERR_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    mec_status st = mixed_plan_locked(ctx, n, present, data_only, item_status);
+    if (st != MEC_OK) return st;
+    return mixed_launch_locked(ctx, shards_dev, shard_len);
+}
+
+mec_status mec_reconstruct_batch_mixed_dev_async(
+    mec_ctx *ctx, int n, void *shards_dev, const uint8_t *present,
+    int64_t shard_len, int data_only, uint8_t *item_status) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return mixed_dev_locked(ctx, n, shards_dev, present, shard_len, data_only,
+                            item_status);
+}
+
+mec_status mec_reconstruct_batch_mixed_dev(mec_ctx *ctx, int n,
+                                           void *shards_dev,
+                                           const uint8_t *present,
+                                           int64_t shard_len, int data_only,
+                                           uint8_t *item_status) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mec_status s = mixed_dev_locked(ctx, n, shards_dev, present, shard_len,
+                                    data_only, item_status);
+    if (s != MEC_OK) return s;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MEC_OK;
+}
+
+mec_status mec_reconstruct_batch_mixed(mec_ctx *ctx, int n, uint8_t *shards,
+                                       const uint8_t *present,
+                                       int64_t shard_len, int data_only,
+                                       uint8_t *item_status) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    if (n <= 0 || !shards || !present || shard_len <= 0 ||
+        shard_len > ctx->stride)
+        return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    mec_status st = mixed_plan_locked(ctx, n, present, data_only, item_status);
+    if (st != MEC_OK) return st;
+    if (ctx->plan.entries.empty()) return MEC_OK; /* nothing to rebuild */
+    const int d = ctx->d, total = ctx->d + ctx->p;
+    const int64_t stride = ctx->stride;
+    const size_t bytes = (size_t)n * total * stride;
+    if ((st = ctx->ensure(&ctx->dev_a, &ctx->cap_a, bytes)) != MEC_OK)
+        return st;
+    if ((st = ctx->ensure_pin(bytes)) != MEC_OK) return st;
+    uint8_t *pinb = (uint8_t *)ctx->pin;
+    /* plain unchunked upload (the uniform call's overlapped ingest is a
+     * follow-up for this path) */
+    for (int64_t b = 0; b < n; b++)
+        for (int s = 0; s < total; s++)
+            memcpy(pinb + ((size_t)b * total + s) * stride,
+                   shards + ((size_t)b * total + s) * shard_len,
+                   (size_t)shard_len);
+    HIP_TRY(hipMemcpyAsync(ctx->dev_a, pinb, bytes, hipMemcpyHostToDevice,
+                           ctx->stream));
+    if ((st = mixed_launch_locked(ctx, ctx->dev_a, shard_len)) != MEC_OK)
+        return st;
+    HIP_TRY(hipMemcpyAsync(pinb, ctx->dev_a, bytes, hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    /* only rebuilt rows go back: unrecoverable and complete items, present
+     * rows, and (data_only) parity rows keep the caller's bytes */
+    for (int64_t b = 0; b < n; b++) {
+        if (ctx->plan.status[b] != mec::kPlanOk) continue;
+        const uint8_t *pr = present + (size_t)b * total;
+        for (int s = 0; s < (data_only ? d : total); s++) {
+            if (pr[s]) continue;
+            memcpy(shards + ((size_t)b * total + s) * shard_len,
+                   pinb + ((size_t)b * total + s) * stride,
+                   (size_t)shard_len);
+        }
+    }
     return MEC_OK;
 }
 

@@ -31,7 +31,23 @@ struct GfMatmulArgs {
     const uint32_t *bs_masks;
 };
 
-/* mode: which shard rows this launch hashes.  Sums always land in the
+/* Mixed-pattern reconstruct (recon_mixed.hip): rows, destinations and bit
+ * matrices come per work item from a device-resident plan table instead
+ * of the kernel arguments.  Table layouts: recon_plan.h. */
+struct GfMixedArgs {
+    uint8_t *shards;         /* batch base, rebuilt in place */
+    int64_t item_stride;     /* bytes between batch items */
+    int64_t row_stride;      /* bytes between shard rows (64-aligned) */
+    int64_t shard_len;       /* valid bytes per shard */
+    const uint32_t *entries; /* plan table, 12 dwords per entry */
+    const uint32_t *masks;   /* packed bit matrices, all entries */
+    const uint32_t *work;    /* this launch's list: (item, entry) pairs */
+    uint32_t n_work;         /* pairs in the list */
+    uint32_t blocks_x;       /* column blocks per pair */
+    int d;                   /* number of source rows */
+};
+
+/* mode: which shard rows this launch hashes. Sums always land in the
  * fused n x (d+p) x digest layout so a data-only and a parity-only launch
  * together produce exactly the single-launch result. */
 enum MecHashMode { MEC_HASH_ALL = 0, MEC_HASH_DATA = 1, MEC_HASH_PARITY = 2 };
@@ -105,6 +121,10 @@ hipError_t mec_launch_fused2_encode_hh(int d, int p, const FusedArgs *args,
                                        hipStream_t stream);
 hipError_t mec_launch_gf_matmul(const GfMatmulArgs *args, int n_dst, int n,
                                 hipStream_t stream);
+/* one launch per output-row count n_dst (1..MEC_KMAX_E); fills
+ * args->blocks_x itself */
+hipError_t mec_launch_gf_matmul_mixed(const GfMixedArgs *args, int n_dst,
+                                      hipStream_t stream);
 hipError_t mec_launch_gf_encode_spec(int d, int p, const GfEncArgs *args,
                                      int n, hipStream_t stream);
 hipError_t mec_launch_hash(int algo, const HashArgs *args, hipStream_t stream);
