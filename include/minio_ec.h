@@ -207,6 +207,72 @@ mec_status mec_reconstruct_batch_mixed(mec_ctx *ctx, int n, uint8_t *shards,
                                        int64_t shard_len, int data_only,
                                        uint8_t *item_status);
 
+/* ---- verified batch read: bitrot check on device, then reconstruct ------
+ *
+ * The mixed calls above take a mask that is already known: the shim must
+ * have bitrot-checked every row before it calls them.  In the reference
+ * the two steps are one operation: streamingBitrotReader.ReadAt
+ * (cmd/bitrot-streaming.go:161-200) returns errFileCorrupt for a block
+ * whose hash does not match, parallelReader.Read
+ * (cmd/erasure-decode.go:127-235) triggers d reads, drops a row that
+ * failed for that block and reads another, and Decode or Heal
+ * (cmd/erasure-decode.go:239-364) reconstructs from what verified.  These
+ * calls do the same for a batch across objects whose rows are in HBM:
+ *   1. bitrot-check, on the GPU, only the rows that were read;
+ *   2. treat a mismatch as a missing row of that item;
+ *   3. rebuild in place through the mixed planner and kernels;
+ *   4. with rehash, write fresh digests for the rebuilt rows, as
+ *      Erasure.Heal does by writing a healed shard through a bitrot writer.
+ *
+ * shards_dev: mec_reconstruct_batch_mixed_dev's layout, n*(d+p)*stride
+ *     bytes, row s of item i at (i*(d+p)+s)*stride, rebuilt in place.
+ * sums_dev:   n*(d+p)*32 bytes in the fused sums layout
+ *     mec_encode_batch_dev writes, so encode output feeds straight back
+ *     in.  On entry the expected digest of every row flagged in read_mask;
+ *     other slots are ignored.  Modified only when rehash != 0: the slots
+ *     of the rebuilt rows of recoverable items then hold the digests of
+ *     the rebuilt bytes; slots of verified rows are never written.
+ * read_mask (host, n*(d+p) bytes): nonzero = the row was read from its
+ *     drive, so its bytes and digest are there.  Zero = dead drive, row
+ *     not fetched yet, or errFileNotFound; such rows are never hashed and
+ *     their bytes and digest slots may hold anything.
+ * bitrot_algo: MEC_BITROT_HIGHWAYHASH256S or MEC_BITROT_HIGHWAYHASH256 (the
+ *     same keyed function; only the streaming format has per-block digests
+ *     at all).  Anything else: MEC_ERR_INVALID_ARG.
+ * present_out (host, n*(d+p) bytes, may be NULL): 1 where the row was read
+ *     and its digest matched, else 0.  read_mask set and present_out 0 is
+ *     a bitrot hit: the shim maps it to errFileCorrupt and queues the
+ *     heal, as parallelReader does with bitrotHeal
+ *     (cmd/erasure-decode.go:197-198, :227-228).
+ * item_status, data_only: mec_reconstruct_batch_mixed_dev's semantics,
+ *     applied to the verified mask.  Fewer than d verified rows:
+ *     item_status[i] = MEC_ERR_TOO_FEW_SHARDS, the item's bytes and digests
+ *     stay untouched, the rest of the batch proceeds; the shim reads more
+ *     rows of that item and calls again.  With item_status NULL any such
+ *     item makes the call return MEC_ERR_TOO_FEW_SHARDS with nothing
+ *     modified; present_out is still filled.  Verified rows are never
+ *     written; a row that failed verification is rebuilt in its slot when
+ *     it is in scope (any row, or data rows only under data_only).
+ *
+ * n*(d+p) must fit in 32 bits (else MEC_ERR_INVALID_ARG); n is not limited
+ * to 65535.  shard_len is one value for the whole call: per-item shard
+ * lengths are out of scope.  The calls are synchronous, since the host
+ * needs the verdicts to plan: one stream synchronise before planning, one
+ * at the end, and no _async variant.  mec_decode_stream and
+ * mec_heal_stream keep their own per-object host grouping.
+ * The host-pointer variant takes rows packed at shard_len and digests
+ * packed at 32 B, packs only the rows flagged in read_mask, uploads in one
+ * plain copy, and writes back only the rebuilt rows (and, with rehash,
+ * their digests). */
+mec_status mec_verify_reconstruct_batch_dev(
+    mec_ctx *ctx, int n, void *shards_dev, void *sums_dev,
+    const uint8_t *read_mask, int64_t shard_len, int bitrot_algo,
+    int data_only, int rehash, uint8_t *present_out, uint8_t *item_status);
+mec_status mec_verify_reconstruct_batch(
+    mec_ctx *ctx, int n, uint8_t *shards, uint8_t *sums,
+    const uint8_t *read_mask, int64_t shard_len, int bitrot_algo,
+    int data_only, int rehash, uint8_t *present_out, uint8_t *item_status);
+
 /* ---- batch bitrot hash / verify ----------------------------------------
  * msgs: n messages of msg_len bytes at msg_stride; sums: n * hash_size.
  * verify: ok_out[i]=1 where digest matches want[i] (errFileCorrupt map). */

@@ -20,6 +20,13 @@ surfaces 1:1 for tests and benchmarks:
                             for many blocks in one call, each with its own
                             erasure pattern (a cross-object degraded read
                             or heal; mec_reconstruct_batch_mixed)
+  - Erasure.verify_reconstruct_batch
+                        <-> streamingBitrotReader.ReadAt + parallelReader.Read
+                            + Decode/Heal for many blocks in one call: rows
+                            that fail their bitrot check count as missing
+                            (cmd/bitrot-streaming.go:161-200,
+                             cmd/erasure-decode.go:127-235;
+                             mec_verify_reconstruct_batch)
   - bitrot_verify       <-> bitrotVerify (cmd/bitrot.go:164-216)
 
 No CPU fallback exists: constructing an Erasure on a machine without a
@@ -105,6 +112,10 @@ def _load():
     lib.mec_reconstruct_batch_mixed.argtypes = [vp, i32, u8p, u8p, i64, i32, u8p]
     lib.mec_reconstruct_batch_mixed_dev.argtypes = [vp, i32, vp, u8p, i64, i32, u8p]
     lib.mec_reconstruct_batch_mixed_dev_async.argtypes = [vp, i32, vp, u8p, i64, i32, u8p]
+    lib.mec_verify_reconstruct_batch_dev.argtypes = [
+        vp, i32, vp, vp, u8p, i64, i32, i32, i32, u8p, u8p]
+    lib.mec_verify_reconstruct_batch.argtypes = [
+        vp, i32, u8p, u8p, u8p, i64, i32, i32, i32, u8p, u8p]
     lib.mec_bitrot_sum_batch.argtypes =[vp, i32, i32, u8p, i64, i64, u8p]
     lib.mec_bitrot_sum_batch_dev.argtypes = [vp, i32, i32, vp, i64, i64, vp]
     lib.mec_bitrot_verify_batch.argtypes = [vp, i32, i32, u8p, i64, i64, u8p, u8p]
@@ -333,6 +344,74 @@ class Erasure:
                     row.append(it[s])
             out.append(row)
         return out, statuses
+
+    def verify_reconstruct_batch(self, items, sums, data_only=False,
+                                 rehash=False,
+                                 algo: int = HIGHWAYHASH256S):
+        """Verified batch read (mec_verify_reconstruct_batch): bitrot-check
+        the rows that were read, treat a mismatch as a missing row of that
+        item, and reconstruct from what verified — streamingBitrotReader.
+        ReadAt + parallelReader.Read + Decode/Heal for many blocks at once.
+
+        items: as in reconstruct_batch, None marking a row that was not
+        read.  sums[i][s]: the row's expected 32-byte digest, or None (rows
+        that were not read need none).  Returns (items_out, sums_out,
+        statuses, corrupt): items_out has the missing and the corrupt rows
+        that are in scope rebuilt (data rows only when data_only) and every
+        other row as given; statuses[i] is 0 or 3 (ErrTooFewShards: fewer
+        than d rows verified, item returned unchanged); corrupt[i] lists
+        the rows that were read and failed their check.  sums_out is None
+        unless rehash: then sums with the rebuilt rows' fresh digests."""
+        total = self.d + self.p
+        n = len(items)
+        if n == 0:
+            return [], ([] if rehash else None), [], []
+        assert len(sums) == n
+        for it, su in zip(items, sums):
+            assert len(it) == total and len(su) == total
+        lens = {len(s) for it in items for s in it if s is not None}
+        if not lens:
+            return ([list(it) for it in items],
+                    [list(su) for su in sums] if rehash else None,
+                    [3] * n, [[] for _ in range(n)])
+        assert len(lens) == 1, "all shards of a batch share one length"
+        per = lens.pop()
+        for it, su in zip(items, sums):
+            for s in range(total):
+                assert it[s] is None or (su[s] is not None
+                                         and len(su[s]) == 32), \
+                    "a row that was read needs its 32-byte digest"
+        read = bytes(0 if s is None else 1 for it in items for s in it)
+        hole, nosum = b"\0" * per, b"\0" * 32
+        buf = ctypes.create_string_buffer(
+            b"".join(hole if s is None else s for it in items for s in it),
+            n * total * per)
+        sbuf = ctypes.create_string_buffer(
+            b"".join(nosum if h is None else h for su in sums for h in su),
+            n * total * 32)
+        present = ctypes.create_string_buffer(n * total)
+        status = ctypes.create_string_buffer(n)
+        _check(_lib.mec_verify_reconstruct_batch(
+            self._ck(), n, buf, sbuf, read, per, algo,
+            1 if data_only else 0, 1 if rehash else 0, present, status))
+        statuses = list(status.raw)
+        pres, raw, sraw = present.raw, buf.raw, sbuf.raw
+        scope = self.d if data_only else total
+        out, sums_out, corrupt = [], ([] if rehash else None), []
+        for i, it in enumerate(items):
+            corrupt.append([s for s in range(total)
+                            if read[i * total + s] and not pres[i * total + s]])
+            row, srow = list(it), list(sums[i])
+            if statuses[i] == MEC_OK:
+                for s in range(scope):
+                    c = i * total + s
+                    if not pres[c]:
+                        row[s] = raw[c * per:(c + 1) * per]
+                        srow[s] = sraw[c * 32:(c + 1) * 32]
+            out.append(row)
+            if rehash:
+                sums_out.append(srow)
+        return out, sums_out, statuses, corrupt
 
     # -- streaming-format drivers (Erasure.Encode / Decode / Heal) --
     def encode_stream(self, src: bytes, algo: int = HIGHWAYHASH256S):

@@ -16,6 +16,7 @@
 #include "gf_host.h"
 #include "kernels.h"
 #include "recon_plan.h"
+#include "verify_list.h"
 
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -114,6 +115,14 @@ struct mec_ctx {
     hipEvent_t ev_x[2] = {nullptr, nullptr};
     int x_idx = 0;
     mec::ReconPlan plan; /* reused across calls to keep its allocations */
+
+    /* verified batch read: dev_v holds [chain-id list | ok bytes], pin_v
+     * stages the list up and the ok bytes down.  The call is synchronous,
+     * so one pinned buffer is enough.  Grow-only, sized by n*(d+p). */
+    void *dev_v = nullptr, *pin_v = nullptr;
+    size_t cap_v = 0, cap_pin_v = 0;
+    std::vector<uint32_t> vlist;   /* verify list, then the rehash list */
+    std::vector<uint8_t> vpresent; /* read_mask & ok */
 
     mec_status ensure(void **buf, size_t *cap, size_t need) {
         if (*cap >= need) return MEC_OK;
@@ -297,6 +306,8 @@ void mec_ctx_destroy(mec_ctx *ctx) {
     if (ctx->dev_d) (void)hipFree(ctx->dev_d);
     if (ctx->dev_m) (void)hipFree(ctx->dev_m);
     if (ctx->dev_x) (void)hipFree(ctx->dev_x);
+    if (ctx->dev_v) (void)hipFree(ctx->dev_v);
+    if (ctx->pin_v) (void)hipHostFree(ctx->pin_v);
     for (int s = 0; s < 2; s++) {
         if (ctx->pin_x[s]) (void)hipHostFree(ctx->pin_x[s]);
         if (ctx->ev_x[s]) (void)hipEventDestroy(ctx->ev_x[s]);
@@ -923,6 +934,187 @@ mec_status mec_reconstruct_batch_mixed(mec_ctx *ctx, int n, uint8_t *shards,
                    pinb + ((size_t)b * total + s) * stride,
                    (size_t)shard_len);
         }
+    }
+    return MEC_OK;
+}
+
+/* ---- verified batch read: bitrot check on device, then reconstruct ------ */
+
+/* The reference does both in one operation: streamingBitrotReader.ReadAt
+ * (cmd/bitrot-streaming.go:161-200) returns errFileCorrupt for a block
+ * whose hash does not match, parallelReader.Read
+ * (cmd/erasure-decode.go:127-235) drops that row and reads another, and
+ * Decode/Heal reconstruct from what verified.
+ *
+ * Verifies the rows read_mask names, plans on read_mask & ok, launches the
+ * mixed kernels and, with rehash, the digests of the rebuilt rows.  One
+ * stream synchronise (the host needs the verdicts to plan); the caller
+ * does the final one.  On return ctx->vpresent is the verified mask and,
+ * with want_rebuilt, ctx->vlist the ids of the rows that were rebuilt. */
+static mec_status verify_recon_locked(mec_ctx *ctx, int n, void *shards_dev,
+                                      void *sums_dev,
+                                      const uint8_t *read_mask,
+                                      int64_t shard_len, int data_only,
+                                      int rehash, bool want_rebuilt,
+                                      uint8_t *present_out,
+                                      uint8_t *item_status) {
+    const int d = ctx->d, p = ctx->p, total = d + p;
+    uint32_t count;
+    if (!mec::verify_chain_count(n, total, &count)) return MEC_ERR_INVALID_ARG;
+    if (!mec::build_verify_list(n, total, read_mask, &ctx->vlist))
+        return MEC_ERR_INVALID_ARG;
+    const size_t n_list = ctx->vlist.size();
+
+    /* [list, room for every chain | ok bytes]: the size depends on the
+     * call's dimensions only, not on its masks */
+    const size_t ok_off = ((size_t)count * sizeof(uint32_t) + 15) & ~(size_t)15;
+    const size_t need = ok_off + count;
+    mec_status st;
+    if ((st = ctx->ensure(&ctx->dev_v, &ctx->cap_v, need)) != MEC_OK)
+        return st;
+    if (ctx->cap_pin_v < need) {
+        if (ctx->pin_v) (void)hipHostFree(ctx->pin_v);
+        ctx->pin_v = nullptr;
+        ctx->cap_pin_v = 0;
+        HIP_TRY(hipHostMalloc(&ctx->pin_v, need));
+        ctx->cap_pin_v = need;
+    }
+    uint8_t *pinb = (uint8_t *)ctx->pin_v;
+    uint8_t *dv = (uint8_t *)ctx->dev_v;
+
+    HashListArgs h{};
+    h.shards = (const uint8_t *)shards_dev;
+    h.sums = (uint8_t *)sums_dev;
+    h.ok = dv + ok_off;
+    h.list = (const uint32_t *)dv;
+    h.row_stride = ctx->stride;
+    h.msg_len = shard_len;
+    memcpy(h.key, kMagicHHKey, 32);
+
+    if (n_list) {
+        memcpy(pinb, ctx->vlist.data(), n_list * sizeof(uint32_t));
+        HIP_TRY(hipMemcpyAsync(dv, pinb, n_list * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(hipMemsetAsync(dv + ok_off, 0, count, ctx->stream));
+    h.n_list = (uint32_t)n_list;
+    HIP_TRY(mec_launch_hash_list(&h, 1, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(pinb + ok_off, dv + ok_off, count,
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+
+    ctx->vpresent.resize(count);
+    mec::merge_verified(count, read_mask, pinb + ok_off,
+                        ctx->vpresent.data());
+    if (present_out) memcpy(present_out, ctx->vpresent.data(), count);
+
+    st = mixed_plan_locked(ctx, n, ctx->vpresent.data(), data_only,
+                           item_status);
+    if (st != MEC_OK) return st;
+    if ((st = mixed_launch_locked(ctx, shards_dev, shard_len)) != MEC_OK)
+        return st;
+
+    ctx->vlist.clear();
+    if ((rehash || want_rebuilt) && !ctx->plan.entries.empty())
+        mec::build_rehash_list(ctx->plan, d, p, n, ctx->vpresent.data(),
+                               data_only, &ctx->vlist);
+    if (rehash && !ctx->vlist.empty()) {
+        /* the verify kernel and the list upload are done (synchronised
+         * above), so both list buffers can be refilled */
+        const size_t nb = ctx->vlist.size() * sizeof(uint32_t);
+        memcpy(pinb, ctx->vlist.data(), nb);
+        HIP_TRY(hipMemcpyAsync(dv, pinb, nb, hipMemcpyHostToDevice,
+                               ctx->stream));
+        h.n_list = (uint32_t)ctx->vlist.size();
+        HIP_TRY(mec_launch_hash_list(&h, 0, ctx->stream));
+    }
+    return MEC_OK;
+}
+
+static bool verify_recon_args_ok(mec_ctx *ctx, int n, const void *shards,
+                                 const void *sums, const uint8_t *read_mask,
+                                 int64_t shard_len, int bitrot_algo) {
+    /* only the streaming format has per-block digests; both ids name the
+     * same keyed function */
+    if (bitrot_algo != MEC_BITROT_HIGHWAYHASH256S &&
+        bitrot_algo != MEC_BITROT_HIGHWAYHASH256)
+        return false;
+    return n > 0 && shards && sums && read_mask && shard_len > 0 &&
+           shard_len <= ctx->stride;
+}
+
+mec_status mec_verify_reconstruct_batch_dev(
+    mec_ctx *ctx, int n, void *shards_dev, void *sums_dev,
+    const uint8_t *read_mask, int64_t shard_len, int bitrot_algo,
+    int data_only, int rehash, uint8_t *present_out, uint8_t *item_status) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    if (!verify_recon_args_ok(ctx, n, shards_dev, sums_dev, read_mask,
+                              shard_len, bitrot_algo))
+        return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    mec_status st = verify_recon_locked(ctx, n, shards_dev, sums_dev,
+                                        read_mask, shard_len, data_only,
+                                        rehash, false, present_out,
+                                        item_status);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MEC_OK;
+}
+
+mec_status mec_verify_reconstruct_batch(
+    mec_ctx *ctx, int n, uint8_t *shards, uint8_t *sums,
+    const uint8_t *read_mask, int64_t shard_len, int bitrot_algo,
+    int data_only, int rehash, uint8_t *present_out, uint8_t *item_status) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    if (!verify_recon_args_ok(ctx, n, shards, sums, read_mask, shard_len,
+                              bitrot_algo))
+        return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int total = ctx->d + ctx->p;
+    uint32_t count;
+    if (!mec::verify_chain_count(n, total, &count)) return MEC_ERR_INVALID_ARG;
+    const int64_t stride = ctx->stride;
+    /* rows, then digests, in one device buffer: one upload */
+    const size_t row_bytes = (size_t)count * stride;
+    const size_t sum_bytes = (size_t)count * 32;
+    mec_status st;
+    if ((st = ctx->ensure(&ctx->dev_a, &ctx->cap_a, row_bytes + sum_bytes)) !=
+        MEC_OK)
+        return st;
+    if ((st = ctx->ensure_pin(row_bytes + sum_bytes)) != MEC_OK) return st;
+    uint8_t *pinb = (uint8_t *)ctx->pin;
+    uint8_t *dev_rows = (uint8_t *)ctx->dev_a;
+    uint8_t *dev_sums = dev_rows + row_bytes;
+    /* only rows that were read are packed; the others' device bytes are
+     * whatever the buffer held, which nothing reads */
+    for (uint32_t c = 0; c < count; c++)
+        if (read_mask[c])
+            memcpy(pinb + (size_t)c * stride, shards + (size_t)c * shard_len,
+                   (size_t)shard_len);
+    memcpy(pinb + row_bytes, sums, sum_bytes);
+    HIP_TRY(hipMemcpyAsync(dev_rows, pinb, row_bytes + sum_bytes,
+                           hipMemcpyHostToDevice, ctx->stream));
+    st = verify_recon_locked(ctx, n, dev_rows, dev_sums, read_mask, shard_len,
+                             data_only, rehash, true, present_out,
+                             item_status);
+    if (st != MEC_OK) return st;
+    if (ctx->vlist.empty()) { /* nothing was rebuilt */
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return MEC_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(pinb, dev_rows,
+                           row_bytes + (rehash ? sum_bytes : 0),
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    /* only rebuilt rows go back, with their fresh digests under rehash */
+    for (uint32_t c : ctx->vlist) {
+        memcpy(shards + (size_t)c * shard_len, pinb + (size_t)c * stride,
+               (size_t)shard_len);
+        if (rehash)
+            memcpy(sums + (size_t)c * 32, pinb + row_bytes + (size_t)c * 32,
+                   32);
     }
     return MEC_OK;
 }

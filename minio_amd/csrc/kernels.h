@@ -65,6 +65,23 @@ struct HashArgs {
     uint64_t key[4];       /* HighwayHash key (little-endian words) */
 };
 
+/* List-driven HighwayHash-256 (hh_list.hip): the chains to hash are named
+ * by a device-resident id list instead of being 0..n_chains-1.  Chain id c
+ * is the row at shards + c*row_stride with its digest slot at sums + c*32
+ * (the fused n x (d+p) x 32 layout when c = item*(d+p)+row).
+ * verify mode compares against the slot and stores ok[c] = 0/1;
+ * sum mode writes the digest into the slot. */
+struct HashListArgs {
+    const uint8_t *shards;
+    uint8_t *sums;        /* verify: read only; sum: written */
+    uint8_t *ok;          /* verify only: one byte per chain ID */
+    const uint32_t *list; /* n_list chain ids */
+    uint32_t n_list;
+    int64_t row_stride;
+    int64_t msg_len;      /* bytes hashed per chain, same for all */
+    uint64_t key[4];
+};
+
 /* Specialized-encode args (constexpr-matrix kernels) */
 struct GfEncArgs {
     const uint8_t *data;
@@ -128,6 +145,10 @@ hipError_t mec_launch_gf_matmul_mixed(const GfMixedArgs *args, int n_dst,
 hipError_t mec_launch_gf_encode_spec(int d, int p, const GfEncArgs *args,
                                      int n, hipStream_t stream);
 hipError_t mec_launch_hash(int algo, const HashArgs *args, hipStream_t stream);
+/* HighwayHash-256 over args->list; verify != 0 selects hh256_list_verify,
+ * else hh256_list_sum.  n_list == 0 launches nothing. */
+hipError_t mec_launch_hash_list(const HashListArgs *args, int verify,
+                                hipStream_t stream);
 }
 
 #endif

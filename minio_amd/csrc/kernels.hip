@@ -30,6 +30,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "hh_quad.h" /* permb, dpp_swap1/2, HH1, hh1_update */
 
 /* ---- GF(2^8) SWAR helpers --------------------------------------------- */
 
@@ -455,11 +456,7 @@ __device__ __forceinline__ const uint8_t *chain_ptr(const HashArgs &a,
  *   zip_even out bytes (LSB..MSB): [A3 B4 A2 A5 | B6 A1 B7 A0]
  *   zip_odd  out bytes:            [B3 A4 B2 B5 | B1 A6 B0 A7]
  * where A = v1[even], B = v1[odd] of the pair.  v_perm pool = {hi:lo},
- * selector byte 12 yields 0x00. */
-__device__ __forceinline__ uint32_t permb(uint32_t hi, uint32_t lo,
-                                          uint32_t sel) {
-    return __builtin_amdgcn_perm(hi, lo, sel);
-}
+ * selector byte 12 yields 0x00.  permb() itself: hh_quad.h. */
 
 __device__ __forceinline__ uint64_t zip_even(uint64_t A, uint64_t B) {
     uint32_t a_lo = (uint32_t)A, a_hi = (uint32_t)(A >> 32);
@@ -696,44 +693,9 @@ __global__ void __launch_bounds__(512) hh256_batch_kernel(HashArgs a) {
  *    v_perm selector),
  *  - loads 8 B/lane/packet (dwordx2), same coalescing (a chain's 4 lanes
  *    cover its 32-B packet contiguously).
+ * The per-lane state and packet update (dpp_swap1/2, HH1, hh1_update) are
+ * in hh_quad.h, shared with the list-driven kernels of hh_list.hip.
  */
-__device__ __forceinline__ uint32_t dpp_swap1(uint32_t v) {
-    /* value from lane ^ 1 (zipper pair partner); quad_perm [1,0,3,2] */
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);
-}
-__device__ __forceinline__ uint32_t dpp_swap2(uint32_t v) {
-    /* value from lane ^ 2 (finalization permute); quad_perm [2,3,0,1] */
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);
-}
-
-struct HH1 {
-    uint64_t v0, v1, mul0, mul1; /* this lane's single HighwayHash lane */
-};
-
-/* One packet update for HH lane j (lane parity selects the zipper hi
- * selector; S1/S2 are parity-independent — see zip_even/zip_odd above). */
-__device__ __forceinline__ void hh1_update(HH1 &s, uint64_t w, uint32_t S3) {
-    s.v1 += s.mul0 + w;
-    s.mul0 ^= (s.v1 & 0xffffffffull) * (s.v0 >> 32);
-    s.v0 += s.mul1;
-    s.mul1 ^= (s.v0 & 0xffffffffull) * (s.v1 >> 32);
-    {
-        uint32_t own_lo = (uint32_t)s.v1, own_hi = (uint32_t)(s.v1 >> 32);
-        uint32_t p_hi = dpp_swap1(own_hi);
-        uint32_t lo = permb(own_hi, own_lo, 0x05020C03u) |
-                      permb(0u, p_hi, 0x0C0C000Cu);
-        uint32_t hi = permb(p_hi, own_lo, S3);
-        s.v0 += ((uint64_t)hi << 32) | lo;
-    }
-    {
-        uint32_t own_lo = (uint32_t)s.v0, own_hi = (uint32_t)(s.v0 >> 32);
-        uint32_t p_hi = dpp_swap1(own_hi);
-        uint32_t lo = permb(own_hi, own_lo, 0x05020C03u) |
-                      permb(0u, p_hi, 0x0C0C000Cu);
-        uint32_t hi = permb(p_hi, own_lo, S3);
-        s.v1 += ((uint64_t)hi << 32) | lo;
-    }
-}
 
 template <bool RAGGED, int WG = 256>
 __global__ void __launch_bounds__(WG) hh256_batch4_kernel(HashArgs a) {
