@@ -140,6 +140,71 @@ mec_status mec_encode_batch_dev_pipe(mec_ctx *ctx, int n,
                                      void *sums_dev);
 mec_status mec_pipe_sync(mec_ctx *ctx);
 
+/* ---- batch encode, one block length PER ITEM ----------------------------
+ *
+ * The calls above take one block_len for the whole batch.  A PUT batch
+ * ACROSS objects is not uniform: Erasure.Encode
+ * (cmd/erasure-encode.go:76-108) calls EncodeData(buf[:n]) with whatever
+ * io.ReadFull returned, so every object of at most one block is a single
+ * short block and the last block of every larger object is short too.  The
+ * lengths cannot be padded to a common one: the shard size is ceil(len/d)
+ * (Split, cmd/erasure-coding.go:81), so another length moves every byte to
+ * another shard and column and changes the parity and all d+p digests.
+ * Here block_lens[i] (host, n entries, each in [1, block_size]) is item i's
+ * own length; the shim's PUT batcher fills it (INTEGRATION.md "Batching
+ * PUTs of different sizes").
+ *
+ * Device layout: packed, defined by the lengths alone.  For item i
+ *   S_i = ceil(len_i/d), stride_i = align64(S_i),
+ *   R_0 = 0, R_{i+1} = R_i + stride_i   (the row-offsets helper below)
+ *   data:   d*R_n bytes; row k of item i at d*R_i + k*stride_i, holding
+ *           Split's contents: min(max(len_i - k*S_i, 0), S_i) valid bytes,
+ *           zero-padded to S_i.  Bytes [S_i, stride_i) are undefined and
+ *           never influence a result.
+ *   parity: p*R_n bytes (output); row t of item i at p*R_i + t*stride_i.
+ *           Bytes past S_i are scratch.
+ *   sums:   n*(d+p)*32 bytes in the fused layout of the uniform calls: the
+ *           digest of row s of item i at (i*(d+p)+s)*32, over exactly S_i
+ *           bytes.  NULL: encode only, nothing is hashed.  Otherwise
+ *           bitrot_algo must be MEC_BITROT_HIGHWAYHASH256S or
+ *           MEC_BITROT_HIGHWAYHASH256 (anything else: MEC_ERR_INVALID_ARG).
+ * A 4 KiB object at EC8+4 so takes 8 rows of 512 B, not of 128 KiB.
+ *
+ * The geometry needs a compiled (d,p) specialization, as the pipelined
+ * encode does; otherwise MEC_ERR_INVALID_ARG with a message in
+ * mec_last_error.  Every argument error (n <= 0, a NULL buffer, a length
+ * outside [1, block_size], n*(d+p) past 32 bits, the algorithm, the
+ * geometry) is reported before anything is launched or written.  n is not
+ * limited to 65535.  Two kernels per call whatever the lengths: the GF
+ * kernel runs over one flattened column space, so short items share waves,
+ * and the hash kernel takes the items longest first.
+ *
+ * The row-offsets helper is pure host math: no context, no GPU.  It writes
+ * R_0..R_n into row_off (n+1 entries) and returns MEC_ERR_INVALID_ARG for
+ * n <= 0, a length outside [1, block_size], or a batch whose chain ids
+ * would not fit in 32 bits (it does not know p, so it checks n*d; the
+ * encode calls check n*(d+p)).
+ * _async does not synchronize the stream (pair with mec_stream_sync);
+ * back-to-back _async calls with different length tables need no sync in
+ * between.  The host-pointer variant takes data as the blocks concatenated,
+ * sum(len_i) bytes, does the Split scatter into pinned staging and one
+ * plain upload (no overlapped ingest), and returns parity packed: item i's
+ * p rows of S_i bytes each at p*sum_{j<i} S_j; sums in the fused layout. */
+mec_status mec_var_row_offsets(int data_shards, int64_t block_size, int n,
+                               const int64_t *block_lens, int64_t *row_off);
+mec_status mec_encode_batch_var_dev(mec_ctx *ctx, int n, const void *data_dev,
+                                    const int64_t *block_lens,
+                                    void *parity_dev, int bitrot_algo,
+                                    void *sums_dev);
+mec_status mec_encode_batch_var_dev_async(mec_ctx *ctx, int n,
+                                          const void *data_dev,
+                                          const int64_t *block_lens,
+                                          void *parity_dev, int bitrot_algo,
+                                          void *sums_dev);
+mec_status mec_encode_batch_var(mec_ctx *ctx, int n, const uint8_t *data,
+                                const int64_t *block_lens, uint8_t *parity,
+                                int bitrot_algo, uint8_t *sums);
+
 /* ---- batch reconstruct (ReconstructData / Reconstruct / Heal kernel) ---
  *
  * shards_dev: n * (d+p) * stride bytes; present[i] != 0 marks shard row i

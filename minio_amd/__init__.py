@@ -15,6 +15,12 @@ surfaces 1:1 for tests and benchmarks:
                             (cmd/erasure-encode.go:76, erasure-decode.go:239,
                              :317) over the streaming bitrot on-disk layout
                             (cmd/bitrot-streaming.go)
+  - Erasure.encode_batch_var, var_row_offsets
+                        <-> EncodeData for many blocks in one call, each
+                            with its own length (a PUT batch across
+                            objects: Erasure.Encode encodes whatever
+                            io.ReadFull returned, cmd/erasure-encode.go:
+                            76-108; mec_encode_batch_var)
   - Erasure.reconstruct_batch
                         <-> DecodeDataBlocks / DecodeDataAndParityBlocks
                             for many blocks in one call, each with its own
@@ -106,6 +112,11 @@ def _load():
     lib.mec_encode_batch_dev_async.argtypes = [vp, i32, vp, i64, vp, i32, vp]
     lib.mec_encode_batch_dev_pipe.argtypes = [vp, i32, vp, i64, vp, i32, vp]
     lib.mec_pipe_sync.argtypes = [vp]
+    i64p = c.POINTER(i64)
+    lib.mec_var_row_offsets.argtypes = [i32, i64, i32, i64p, i64p]
+    lib.mec_encode_batch_var.argtypes = [vp, i32, u8p, i64p, u8p, i32, u8p]
+    lib.mec_encode_batch_var_dev.argtypes = [vp, i32, vp, i64p, vp, i32, vp]
+    lib.mec_encode_batch_var_dev_async.argtypes = [vp, i32, vp, i64p, vp, i32, vp]
     lib.mec_reconstruct_batch.argtypes = [vp, i32, u8p, u8p, i64, i32]
     lib.mec_reconstruct_batch_dev.argtypes = [vp, i32, vp, u8p, i64, i32]
     lib.mec_reconstruct_batch_dev_async.argtypes = [vp, i32, vp, u8p, i64, i32]
@@ -173,6 +184,18 @@ def shard_file_offset(block_size: int, d: int, start: int, length: int,
 
 def bitrot_shard_file_size(size: int, shard_size_: int, algo: int) -> int:
     return _lib.mec_bitrot_shard_file_size(size, shard_size_, algo)
+
+
+def var_row_offsets(d: int, block_size: int, lens) -> list:
+    """Row offsets R_0..R_n of the packed per-item-length encode layout
+    (mec_var_row_offsets): R_{i+1} = R_i + align64(ceil(lens[i]/d)).  Item
+    i's data rows start at d*R_i, its parity rows at p*R_i.  Raises
+    MecError(6) for an empty list or a length outside [1, block_size]."""
+    n = len(lens)
+    arr = (ctypes.c_int64 * max(n, 1))(*lens)
+    out = (ctypes.c_int64 * (n + 1))()
+    _check(_lib.mec_var_row_offsets(d, block_size, n, arr, out))
+    return list(out)
 
 
 class Erasure:
@@ -263,6 +286,45 @@ class Erasure:
                     sums_buf.raw[(b * t + s) * hs:(b * t + s + 1) * hs]
                     for s in range(t)
                 ])
+        return out, sums
+
+    def encode_batch_var(self, blocks, algo: int = None):
+        """Encode many blocks in one call, each with its OWN length in
+        [1, block_size] — what a PUT batch across objects produces, since
+        Erasure.Encode hands EncodeData whatever io.ReadFull returned
+        (cmd/erasure-encode.go:76-108; mec_encode_batch_var).
+
+        blocks: list of bytes.  Returns (shards, sums) in the shape of
+        encode_batch: shards[b][s] is ceil(len(blocks[b])/d) bytes (data
+        shards zero-padded), sums[b][s] the 32-byte digests or None.  algo
+        must be HIGHWAYHASH256S or HIGHWAYHASH256 when given."""
+        n = len(blocks)
+        if n == 0:
+            return [], ([] if algo is not None else None)
+        d, p, t = self.d, self.p, self.d + self.p
+        lens = (ctypes.c_int64 * n)(*[len(b) for b in blocks])
+        sizes = [shard_size(len(b), d) for b in blocks]
+        parity = ctypes.create_string_buffer(max(p * sum(sizes), 1))
+        sums_buf = None
+        if algo is not None:
+            sums_buf = ctypes.create_string_buffer(n * t * 32)
+        _check(_lib.mec_encode_batch_var(self._ck(), n, b"".join(blocks),
+                                         lens, parity, algo or 0, sums_buf))
+        praw = parity.raw
+        sraw = sums_buf.raw if sums_buf is not None else None
+        out, sums, off = [], ([] if algo is not None else None), 0
+        for b, (blk, S) in enumerate(zip(blocks, sizes)):
+            shards = []
+            for k in range(d):
+                sh = blk[k * S:(k + 1) * S]
+                shards.append(sh + b"\0" * (S - len(sh)))
+            for i in range(p):
+                shards.append(praw[off:off + S])
+                off += S
+            out.append(shards)
+            if sraw is not None:
+                sums.append([sraw[(b * t + s) * 32:(b * t + s + 1) * 32]
+                             for s in range(t)])
         return out, sums
 
     # -- DecodeDataBlocks / DecodeDataAndParityBlocks --

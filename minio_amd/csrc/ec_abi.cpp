@@ -16,6 +16,7 @@
 #include "gf_host.h"
 #include "kernels.h"
 #include "recon_plan.h"
+#include "var_plan.h"
 #include "verify_list.h"
 
 #include <hip/hip_runtime.h>
@@ -123,6 +124,18 @@ struct mec_ctx {
     size_t cap_v = 0, cap_pin_v = 0;
     std::vector<uint32_t> vlist;   /* verify list, then the rehash list */
     std::vector<uint8_t> vpresent; /* read_mask & ok */
+
+    /* per-item-length encode: the tables of one call (items, column
+     * prefix, hash order) live in dev_e and get there as the mixed
+     * reconstruct's plan does: a stream-ordered copy from one of two pinned
+     * slots, ev_e[s] marking slot s's copy done. */
+    void *dev_e = nullptr;
+    size_t cap_e = 0;
+    void *pin_e[2] = {nullptr, nullptr};
+    size_t cap_pin_e[2] = {0, 0};
+    hipEvent_t ev_e[2] = {nullptr, nullptr};
+    int e_idx = 0;
+    mec::VarPlan vplan; /* reused across calls to keep its allocations */
 
     mec_status ensure(void **buf, size_t *cap, size_t need) {
         if (*cap >= need) return MEC_OK;
@@ -308,6 +321,11 @@ void mec_ctx_destroy(mec_ctx *ctx) {
     if (ctx->dev_x) (void)hipFree(ctx->dev_x);
     if (ctx->dev_v) (void)hipFree(ctx->dev_v);
     if (ctx->pin_v) (void)hipHostFree(ctx->pin_v);
+    if (ctx->dev_e) (void)hipFree(ctx->dev_e);
+    for (int s = 0; s < 2; s++) {
+        if (ctx->pin_e[s]) (void)hipHostFree(ctx->pin_e[s]);
+        if (ctx->ev_e[s]) (void)hipEventDestroy(ctx->ev_e[s]);
+    }
     for (int s = 0; s < 2; s++) {
         if (ctx->pin_x[s]) (void)hipHostFree(ctx->pin_x[s]);
         if (ctx->ev_x[s]) (void)hipEventDestroy(ctx->ev_x[s]);
@@ -620,6 +638,207 @@ mec_status mec_encode_batch(mec_ctx *ctx, int n, const uint8_t *data,
         for (int i = 0; i < p; i++)
             memcpy(parity + ((size_t)b * p + i) * S,
                    pinb + ((size_t)b * p + i) * stride, (size_t)S);
+    if (sums) memcpy(sums, pinb + par_bytes, sum_bytes);
+    return MEC_OK;
+}
+
+/* ---- batch encode, one block length PER ITEM ---------------------------- */
+
+mec_status mec_var_row_offsets(int d, int64_t block_size, int n,
+                               const int64_t *block_lens, int64_t *row_off) {
+    /* p is not known here: the 32-bit chain-id guard is applied to n*d;
+     * the encode calls apply it to n*(d+p) */
+    mec::VarPlan pl;
+    if (!row_off ||
+        !mec::build_var_plan(d, d, block_size, n, block_lens, &pl))
+        return MEC_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++) row_off[i] = pl.items[(size_t)i].row_off;
+    row_off[n] = pl.rows_total;
+    return MEC_OK;
+}
+
+/* Everything that can be refused is refused here, before anything is
+ * launched or written; on MEC_OK ctx->vplan holds the call's plan. */
+static mec_status var_check_locked(mec_ctx *ctx, int n, const void *data,
+                                   const int64_t *block_lens,
+                                   const void *parity, int algo,
+                                   const void *sums) {
+    if (n <= 0 || !data || !block_lens || !parity) return MEC_ERR_INVALID_ARG;
+    /* only HighwayHash has a per-item-length kernel; both ids name the
+     * same keyed function */
+    if (sums && algo != MEC_BITROT_HIGHWAYHASH256S &&
+        algo != MEC_BITROT_HIGHWAYHASH256)
+        return MEC_ERR_INVALID_ARG;
+    if (!mec_encode_var_supported(ctx->d, ctx->p)) {
+        g_last_error = "per-item-length encode needs a compiled (d,p) "
+                       "specialization; EC" + std::to_string(ctx->d) + "+" +
+                       std::to_string(ctx->p) + " has none";
+        return MEC_ERR_INVALID_ARG;
+    }
+    if (!mec::build_var_plan(ctx->d, ctx->d + ctx->p, ctx->block_size, n,
+                             block_lens, &ctx->vplan))
+        return MEC_ERR_INVALID_ARG;
+    return MEC_OK;
+}
+
+/* Uploads ctx->vplan's tables and launches the two kernels.  Never
+ * synchronizes the stream; the only host wait is on the copy that last
+ * read the pinned slot being refilled (two calls back). */
+static mec_status var_launch_locked(mec_ctx *ctx, const void *data_dev,
+                                    void *parity_dev, void *sums_dev) {
+    const mec::VarPlan &pl = ctx->vplan;
+    const size_t n = pl.items.size();
+    auto al16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t item_bytes = n * sizeof(mec::VarItem);
+    const size_t col_off = al16(item_bytes);
+    const size_t col_bytes = (n + 1) * sizeof(int64_t);
+    const size_t ord_off = al16(col_off + col_bytes);
+    const size_t end = al16(ord_off + n * sizeof(uint32_t));
+
+    const int slot = ctx->e_idx & 1;
+    ctx->e_idx ^= 1;
+    if (!ctx->ev_e[slot])
+        HIP_TRY(hipEventCreateWithFlags(&ctx->ev_e[slot],
+                                        hipEventDisableTiming));
+    else
+        HIP_TRY(hipEventSynchronize(ctx->ev_e[slot]));
+    if (ctx->cap_pin_e[slot] < end) {
+        if (ctx->pin_e[slot]) (void)hipHostFree(ctx->pin_e[slot]);
+        ctx->pin_e[slot] = nullptr;
+        ctx->cap_pin_e[slot] = 0;
+        HIP_TRY(hipHostMalloc(&ctx->pin_e[slot], end * 2));
+        ctx->cap_pin_e[slot] = end * 2;
+    }
+    /* growing dev_e frees the old buffer, which waits for the kernels
+     * still reading it; grow with slack so that stays rare */
+    if (ctx->cap_e < end) {
+        mec_status st = ctx->ensure(&ctx->dev_e, &ctx->cap_e, end * 2);
+        if (st != MEC_OK) return st;
+    }
+    uint8_t *pinb = (uint8_t *)ctx->pin_e[slot];
+    memcpy(pinb, pl.items.data(), item_bytes);
+    memcpy(pinb + col_off, pl.col_off.data(), col_bytes);
+    memcpy(pinb + ord_off, pl.order.data(), n * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(ctx->dev_e, pinb, end, hipMemcpyHostToDevice,
+                           ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_e[slot], ctx->stream));
+
+    const uint8_t *de = (const uint8_t *)ctx->dev_e;
+    EncVarArgs a{};
+    a.data = (const uint8_t *)data_dev;
+    a.parity = (uint8_t *)parity_dev;
+    a.sums = (uint8_t *)sums_dev;
+    a.items = (const int64_t *)de;
+    a.col_off = (const int64_t *)(de + col_off);
+    a.order = (const uint32_t *)(de + ord_off);
+    a.cols_total = pl.cols_total;
+    a.n = (uint32_t)n;
+    a.d = ctx->d;
+    a.p = ctx->p;
+    memcpy(a.key, kMagicHHKey, 32);
+    hipError_t he = mec_launch_encode_var(&a, ctx->stream);
+    if (he != hipSuccess) {
+        set_err("encode_var", he);
+        return MEC_ERR_HIP;
+    }
+    return MEC_OK;
+}
+
+mec_status mec_encode_batch_var_dev_async(mec_ctx *ctx, int n,
+                                          const void *data_dev,
+                                          const int64_t *block_lens,
+                                          void *parity_dev, int bitrot_algo,
+                                          void *sums_dev) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mec_status st = var_check_locked(ctx, n, data_dev, block_lens, parity_dev,
+                                     bitrot_algo, sums_dev);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return var_launch_locked(ctx, data_dev, parity_dev, sums_dev);
+}
+
+mec_status mec_encode_batch_var_dev(mec_ctx *ctx, int n, const void *data_dev,
+                                    const int64_t *block_lens,
+                                    void *parity_dev, int bitrot_algo,
+                                    void *sums_dev) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mec_status st = var_check_locked(ctx, n, data_dev, block_lens, parity_dev,
+                                     bitrot_algo, sums_dev);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipSetDevice(ctx->device));
+    st = var_launch_locked(ctx, data_dev, parity_dev, sums_dev);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MEC_OK;
+}
+
+mec_status mec_encode_batch_var(mec_ctx *ctx, int n, const uint8_t *data,
+                                const int64_t *block_lens, uint8_t *parity,
+                                int bitrot_algo, uint8_t *sums) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mec_status st = var_check_locked(ctx, n, data, block_lens, parity,
+                                     bitrot_algo, sums);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const mec::VarPlan &pl = ctx->vplan;
+    const int d = ctx->d, p = ctx->p;
+    const size_t data_bytes = (size_t)d * pl.rows_total;
+    const size_t par_bytes = (size_t)p * pl.rows_total;
+    const size_t sum_bytes = sums ? (size_t)n * (d + p) * 32 : 0;
+    if ((st = ctx->ensure(&ctx->dev_a, &ctx->cap_a, data_bytes)) != MEC_OK)
+        return st;
+    if ((st = ctx->ensure(&ctx->dev_b, &ctx->cap_b, par_bytes)) != MEC_OK)
+        return st;
+    if (sums &&
+        (st = ctx->ensure(&ctx->dev_c, &ctx->cap_c, sum_bytes)) != MEC_OK)
+        return st;
+    if ((st = ctx->ensure_pin(data_bytes > par_bytes + sum_bytes
+                                  ? data_bytes
+                                  : par_bytes + sum_bytes)) != MEC_OK)
+        return st;
+
+    /* Split scatter (cmd/erasure-coding.go:81) of each block into its own
+     * rows: shard k gets bytes [k*S_i, (k+1)*S_i), zero-padded to S_i.
+     * Plain unchunked upload, as mec_reconstruct_batch_mixed. */
+    uint8_t *pinb = (uint8_t *)ctx->pin;
+    const uint8_t *blk = data;
+    for (int b = 0; b < n; b++) {
+        const int64_t S = pl.items[(size_t)b].shard_len;
+        const int64_t stride = (S + 63) & ~int64_t(63);
+        uint8_t *rows = pinb + (size_t)d * pl.items[(size_t)b].row_off;
+        for (int k = 0; k < d; k++) {
+            uint8_t *dst = rows + (size_t)k * stride;
+            int64_t have = block_lens[b] - (int64_t)k * S;
+            if (have < 0) have = 0;
+            if (have > S) have = S;
+            if (have) memcpy(dst, blk + (int64_t)k * S, (size_t)have);
+            if (have < S) memset(dst + have, 0, (size_t)(S - have));
+        }
+        blk += block_lens[b];
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->dev_a, pinb, data_bytes, hipMemcpyHostToDevice,
+                           ctx->stream));
+    st = var_launch_locked(ctx, ctx->dev_a, ctx->dev_b,
+                           sums ? ctx->dev_c : nullptr);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipMemcpyAsync(pinb, ctx->dev_b, par_bytes, hipMemcpyDeviceToHost,
+                           ctx->stream));
+    if (sums)
+        HIP_TRY(hipMemcpyAsync(pinb + par_bytes, ctx->dev_c, sum_bytes,
+                               hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    /* gather parity packed: item b's p rows of S_b bytes */
+    uint8_t *out = parity;
+    for (int b = 0; b < n; b++) {
+        const int64_t S = pl.items[(size_t)b].shard_len;
+        const int64_t stride = (S + 63) & ~int64_t(63);
+        const uint8_t *rows = pinb + (size_t)p * pl.items[(size_t)b].row_off;
+        for (int t = 0; t < p; t++, out += S)
+            memcpy(out, rows + (size_t)t * stride, (size_t)S);
+    }
     if (sums) memcpy(sums, pinb + par_bytes, sum_bytes);
     return MEC_OK;
 }

@@ -90,6 +90,21 @@ struct GfEncArgs {
     int64_t shard_len;
 };
 
+/* Encode with a block length per item (encode_var.hip).  The packed layout
+ * and the three tables are the planner's: var_plan.h. */
+struct EncVarArgs {
+    const uint8_t *data;    /* d * R_n */
+    uint8_t *parity;        /* p * R_n (output) */
+    uint8_t *sums;          /* n * (d+p) * 32 (output); NULL: encode only */
+    const int64_t *items;   /* 2 per item: R_i, S_i (mec::VarItem) */
+    const int64_t *col_off; /* n+1: prefix of 32-byte column counts */
+    const uint32_t *order;  /* n: items by descending S_i (hash order) */
+    int64_t cols_total;     /* col_off[n] */
+    uint32_t n;
+    int d, p;
+    uint64_t key[4];
+};
+
 /* Fused single-pass encode+HighwayHash (fused.hip) */
 struct FusedArgs {
     const uint8_t *data; /* n * d * row_stride */
@@ -144,6 +159,11 @@ hipError_t mec_launch_gf_matmul_mixed(const GfMixedArgs *args, int n_dst,
                                       hipStream_t stream);
 hipError_t mec_launch_gf_encode_spec(int d, int p, const GfEncArgs *args,
                                      int n, hipStream_t stream);
+/* 1 when (d,p) has a compiled gf_encode_bs_var_kernel specialization */
+int mec_encode_var_supported(int d, int p);
+/* gf_encode_bs_var_kernel, then hh256_var_kernel unless args->sums is NULL;
+ * hipErrorNotSupported, with nothing launched, for an unspecialized (d,p) */
+hipError_t mec_launch_encode_var(const EncVarArgs *args, hipStream_t stream);
 hipError_t mec_launch_hash(int algo, const HashArgs *args, hipStream_t stream);
 /* HighwayHash-256 over args->list; verify != 0 selects hh256_list_verify,
  * else hh256_list_sum.  n_list == 0 launches nothing. */
