@@ -89,6 +89,11 @@ struct mec_ctx {
     hipEvent_t ev_gf = nullptr, ev_h = nullptr, ev_fork = nullptr;
     hipEvent_t ev_pipe[2] = {nullptr, nullptr}; /* hash-done per buffer slot */
     int pipe_idx = 0;
+    /* Which batches the one-pass fused4 kernel takes (f4_takes).  Read
+     * per context at mec_ctx_create, never latched: f4_min_n is MEC_F4_MIN,
+     * -1 when unset; f4_cus the device's compute-unit count. */
+    int f4_min_n = -1;
+    int f4_cus = 0;
     std::mutex mu;
 
     /* grow-only scratch (device + pinned host) for host-pointer calls */
@@ -237,6 +242,9 @@ mec_status mec_ctx_create(int d, int p, int64_t block_size, int device,
         delete ctx;
         return MEC_ERR_INVALID_ARG;
     }
+    if (const char *s = getenv("MEC_F4_MIN")) ctx->f4_min_n = atoi(s);
+    (void)hipDeviceGetAttribute(&ctx->f4_cus,
+                                hipDeviceAttributeMultiprocessorCount, device);
     hipError_t e = hipSetDevice(device);
     /* MEC_CU_SPLIT=H: partition the chip so the latency-bound hash lane
      * (stream2) gets H CUs EXCLUSIVELY and the memory-bound GF lane
@@ -345,6 +353,20 @@ void mec_ctx_destroy(mec_ctx *ctx) {
 
 /* ---- batch encode ------------------------------------------------------ */
 
+/* fused4 runs one workgroup of 4 blocks per compute unit, so a launch
+ * costs whole rounds of f4_cus workgroups, while the kernel pair scales
+ * with n: fused4 wins when its rounds are at least 3/4 full.  Measured at
+ * EC8+4/1 MiB on 256 CUs: it wins at n = 768, 896,
+ * 1024 and 2048 (fill 0.75 to 1) and loses at 1280 (0.625).  With
+ * MEC_F4_MIN set, n >= MEC_F4_MIN decides alone. */
+static bool f4_takes(const mec_ctx *ctx, int n) {
+    if (ctx->f4_min_n >= 0) return n >= ctx->f4_min_n;
+    if (ctx->f4_cus <= 0) return false;
+    const int64_t wgs = ((int64_t)n + 3) / 4;
+    const int64_t rounds = (wgs + ctx->f4_cus - 1) / ctx->f4_cus;
+    return wgs * 4 >= rounds * ctx->f4_cus * 3;
+}
+
 static mec_status encode_dev_locked(mec_ctx *ctx, int n, const void *data_dev,
                                     int64_t block_len, void *parity_dev,
                                     int algo, void *sums_dev) {
@@ -386,6 +408,14 @@ static mec_status encode_dev_locked(mec_ctx *ctx, int n, const void *data_dev,
         if (he != hipErrorNotSupported) {
             set_err("fused_encode_hh", he);
             return MEC_ERR_HIP;
+        }
+        if (f4_takes(ctx, n)) {
+            he = mec_launch_fused4_encode_hh(d, p, &fa, ctx->stream);
+            if (he == hipSuccess) return MEC_OK;
+            if (he != hipErrorNotSupported) {
+                set_err("fused4_encode_hh", he);
+                return MEC_ERR_HIP;
+            }
         }
     }
     /* specialized straight-line kernel for common geometries */
@@ -513,6 +543,17 @@ mec_status mec_encode_batch_dev_pipe(mec_ctx *ctx, int n,
         if (he != hipErrorNotSupported) {
             set_err("fused3_encode_hh", he);
             return MEC_ERR_HIP;
+        }
+        if (f4_takes(ctx, n)) {
+            he = mec_launch_fused4_encode_hh(d, p, &fa, ctx->stream);
+            if (he == hipSuccess) {
+                HIP_TRY(hipEventRecord(ctx->ev_pipe[idx], ctx->stream));
+                return MEC_OK;
+            }
+            if (he != hipErrorNotSupported) {
+                set_err("fused4_encode_hh", he);
+                return MEC_ERR_HIP;
+            }
         }
     }
     {

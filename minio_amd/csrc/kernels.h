@@ -151,6 +151,13 @@ hipError_t mec_launch_fused3_encode_hh(int d, int p, const FusedArgs *args,
                                        hipStream_t stream);
 hipError_t mec_launch_fused2_encode_hh(int d, int p, const FusedArgs *args,
                                        hipStream_t stream);
+/* one-pass kernel of fused4.hip; hipErrorNotSupported, with nothing
+ * launched, when the shape is not eligible or a knob turns it off */
+hipError_t mec_launch_fused4_encode_hh(int d, int p, const FusedArgs *args,
+                                       hipStream_t stream);
+/* fused4 launches by this process so far: lets a test tell the one-pass
+ * kernel from the pair, whose results are the same */
+uint64_t mec_fused4_launches(void);
 hipError_t mec_launch_gf_matmul(const GfMatmulArgs *args, int n_dst, int n,
                                 hipStream_t stream);
 /* one launch per output-row count n_dst (1..MEC_KMAX_E); fills
