@@ -86,7 +86,7 @@ struct mec_ctx {
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr; /* hash(data) overlap lane */
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    hipEvent_t ev_gf = nullptr, ev_h = nullptr, ev_fork = nullptr;
+    hipEvent_t ev_gf = nullptr, ev_h = nullptr;
     hipEvent_t ev_pipe[2] = {nullptr, nullptr}; /* hash-done per buffer slot */
     int pipe_idx = 0;
     /* Which batches the one-pass fused4 kernel takes (f4_takes).  Read
@@ -246,63 +246,12 @@ mec_status mec_ctx_create(int d, int p, int64_t block_size, int device,
     (void)hipDeviceGetAttribute(&ctx->f4_cus,
                                 hipDeviceAttributeMultiprocessorCount, device);
     hipError_t e = hipSetDevice(device);
-    /* MEC_CU_SPLIT=H: partition the chip so the latency-bound hash lane
-     * (stream2) gets H CUs EXCLUSIVELY and the memory-bound GF lane
-     * (stream) the rest.  Overlapped gf/hash waves sharing a SIMD stretch
-     * the hash ~1.5x (issue-slot contention); an exclusive partition
-     * removes that.  CUs are spread round-robin so both lanes touch every
-     * XCD's L2/HBM channels.  0/unset = classic shared streams. */
-    int cu_split = 0;
-    if (const char *s = getenv("MEC_CU_SPLIT")) cu_split = atoi(s);
-    if (cu_split > 0) {
-        int ncu = 0;
-        (void)hipDeviceGetAttribute(&ncu,
-                                    hipDeviceAttributeMultiprocessorCount,
-                                    device);
-        if (ncu <= 0 || cu_split >= ncu) cu_split = 0;
-        if (cu_split > 0) {
-            uint32_t mh[8] = {0}, mg[8] = {0};
-            int given = 0;
-            for (int i = 0; i < ncu && i < 256; i++) {
-                /* spread hash CUs evenly across the index space (and so
-                 * across XCDs, which interleave in the physical mapping) */
-                bool h = ((int64_t)(i + 1) * cu_split / ncu) >
-                         ((int64_t)i * cu_split / ncu);
-                if (h) {
-                    mh[i >> 5] |= 1u << (i & 31);
-                    given++;
-                } else {
-                    mg[i >> 5] |= 1u << (i & 31);
-                }
-            }
-            (void)given;
-            /* note: gfx950 silently IGNORES CU masks (measured flat in the
-             * r1 sweep) — the knob is a recorded no-op there.  If masked
-             * stream creation fails, fall back to plain streams: this is a
-             * tuning knob, never a correctness dependency. */
-            if (e == hipSuccess) {
-                hipError_t em =
-                    hipExtStreamCreateWithCUMask(&ctx->stream, 8, mg);
-                if (em == hipSuccess)
-                    em = hipExtStreamCreateWithCUMask(&ctx->stream2, 8, mh);
-                if (em != hipSuccess) {
-                    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-                    ctx->stream = nullptr;
-                    ctx->stream2 = nullptr;
-                    cu_split = 0; /* plain-stream fallback below */
-                }
-            }
-        }
-    }
-    if (cu_split <= 0) {
-        if (e == hipSuccess) e = hipStreamCreate(&ctx->stream);
-        if (e == hipSuccess) e = hipStreamCreate(&ctx->stream2);
-    }
+    if (e == hipSuccess) e = hipStreamCreate(&ctx->stream);
+    if (e == hipSuccess) e = hipStreamCreate(&ctx->stream2);
     if (e == hipSuccess) e = hipEventCreate(&ctx->ev_start);
     if (e == hipSuccess) e = hipEventCreate(&ctx->ev_stop);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_gf, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_h, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_pipe[0], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_pipe[1], hipEventDisableTiming);
     if (e != hipSuccess) {
@@ -343,7 +292,6 @@ void mec_ctx_destroy(mec_ctx *ctx) {
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->ev_gf) (void)hipEventDestroy(ctx->ev_gf);
     if (ctx->ev_h) (void)hipEventDestroy(ctx->ev_h);
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_pipe[0]) (void)hipEventDestroy(ctx->ev_pipe[0]);
     if (ctx->ev_pipe[1]) (void)hipEventDestroy(ctx->ev_pipe[1]);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -367,6 +315,112 @@ static bool f4_takes(const mec_ctx *ctx, int n) {
     return wgs * 4 >= rounds * ctx->f4_cus * 3;
 }
 
+/* What became of a batch offered to the one-pass kernel. */
+enum class F4 { Launched, NotTaken, Error };
+
+/* One-pass encode + HighwayHash (fused4.hip; 1.5 B of HBM traffic per
+ * input byte vs 3.0 for the kernel pair) on ctx->stream, for the batches
+ * f4_takes gives it.  NotTaken: nothing was launched and the caller runs
+ * the kernel pair.  Error: set_err has been called. */
+static F4 try_fused4(mec_ctx *ctx, int n, const void *data_dev,
+                     int64_t shard_len, void *parity_dev, int algo,
+                     void *sums_dev) {
+    if (algo != MEC_BITROT_HIGHWAYHASH256 &&
+        algo != MEC_BITROT_HIGHWAYHASH256S)
+        return F4::NotTaken;
+    if (!f4_takes(ctx, n)) return F4::NotTaken;
+    FusedArgs fa{};
+    fa.data = (const uint8_t *)data_dev;
+    fa.parity = (uint8_t *)parity_dev;
+    fa.sums = (uint8_t *)sums_dev;
+    fa.row_stride = ctx->stride;
+    fa.shard_len = shard_len;
+    fa.n = n;
+    memcpy(fa.key, kMagicHHKey, 32);
+    hipError_t he =
+        mec_launch_fused4_encode_hh(ctx->d, ctx->p, &fa, ctx->stream);
+    if (he == hipSuccess) return F4::Launched;
+    if (he == hipErrorNotSupported) return F4::NotTaken;
+    set_err("fused4_encode_hh", he);
+    return F4::Error;
+}
+
+/* Bitrot sums of every data and parity row of an encoded batch, one launch
+ * on `stream`. */
+static mec_status hash_all_rows(mec_ctx *ctx, int n, const void *data_dev,
+                                int64_t shard_len, const void *parity_dev,
+                                int algo, void *sums_dev,
+                                hipStream_t stream) {
+    HashArgs h{};
+    h.data = (const uint8_t *)data_dev;
+    h.parity = (const uint8_t *)parity_dev;
+    h.sums = (uint8_t *)sums_dev;
+    h.row_stride = ctx->stride;
+    h.msg_len = shard_len;
+    h.d = ctx->d;
+    h.p = ctx->p;
+    h.mode = MEC_HASH_ALL;
+    h.n_chains = (int64_t)n * (ctx->d + ctx->p);
+    memcpy(h.key, kMagicHHKey, 32);
+    HIP_TRY(mec_launch_hash(algo, &h, stream));
+    return MEC_OK;
+}
+
+/* Pack the e x d coefficients of mat (rows MEC_KMAX_D apart, as in
+ * GfMatmulArgs::mat) into 8x8 bit matrices, make dev_m hold them and
+ * return it in *masks_dev.  A few hundred bytes, uploaded synchronously,
+ * and only when they differ from what dev_m already holds (m_cached). */
+static mec_status bs_masks_dev(mec_ctx *ctx, const uint8_t *mat, int e, int d,
+                               const uint32_t **masks_dev) {
+    uint32_t masks[MEC_KMAX_E * MEC_KMAX_D * 2];
+    for (int i = 0; i < e; i++)
+        for (int k = 0; k < d; k++)
+            bs_pack_matrix(mat[i * MEC_KMAX_D + k],
+                           &masks[((size_t)i * d + k) * 2]);
+    size_t mw = (size_t)e * d * 2;
+    size_t mb = mw * sizeof(uint32_t);
+    if (ctx->m_cached.size() != mw ||
+        memcmp(ctx->m_cached.data(), masks, mb) != 0) {
+        mec_status st;
+        if ((st = ctx->ensure(&ctx->dev_m, &ctx->cap_m, mb)) != MEC_OK)
+            return st;
+        /* prior launches may still read dev_m */
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(hipMemcpy(ctx->dev_m, masks, mb, hipMemcpyHostToDevice));
+        ctx->m_cached.assign(masks, masks + mw);
+    }
+    *masks_dev = (const uint32_t *)ctx->dev_m;
+    return MEC_OK;
+}
+
+/* Encode for a geometry without a compiled specialization: GF parity rows
+ * by the runtime-matrix kernel, in groups of <= MEC_KMAX_E. */
+static mec_status encode_generic(mec_ctx *ctx, int n, const void *data_dev,
+                                 int64_t shard_len, void *parity_dev) {
+    const int d = ctx->d, p = ctx->p;
+    for (int i0 = 0; i0 < p; i0 += MEC_KMAX_E) {
+        int e = p - i0 > MEC_KMAX_E ? MEC_KMAX_E : p - i0;
+        GfMatmulArgs a{};
+        a.src = (const uint8_t *)data_dev;
+        a.dst = (uint8_t *)parity_dev;
+        a.src_item_stride = (int64_t)d * ctx->stride;
+        a.dst_item_stride = (int64_t)p * ctx->stride;
+        a.row_stride = ctx->stride;
+        a.shard_len = shard_len;
+        a.d = d;
+        for (int k = 0; k < d; k++) a.src_rows[k] = (uint8_t)k;
+        for (int i = 0; i < e; i++) a.dst_rows[i] = (uint8_t)(i0 + i);
+        for (int i = 0; i < e; i++)
+            for (int k = 0; k < d; k++)
+                a.mat[i * MEC_KMAX_D + k] =
+                    ctx->enc_matrix[(size_t)(d + i0 + i) * d + k];
+        mec_status st = bs_masks_dev(ctx, a.mat, e, d, &a.bs_masks);
+        if (st != MEC_OK) return st;
+        HIP_TRY(mec_launch_gf_matmul(&a, e, n, ctx->stream));
+    }
+    return MEC_OK;
+}
+
 static mec_status encode_dev_locked(mec_ctx *ctx, int n, const void *data_dev,
                                     int64_t block_len, void *parity_dev,
                                     int algo, void *sums_dev) {
@@ -378,103 +432,30 @@ static mec_status encode_dev_locked(mec_ctx *ctx, int n, const void *data_dev,
     /* per-call shard size mirrors Split: ceil(block_len/d)
      * (cmd/erasure-coding.go:81 + :117); rows stay at ctx->stride */
     const int64_t S_call = ceil_frac(block_len, d);
-    /* single-pass fused encode+hash for HighwayHash geometries with a
-     * compiled specialization (1.5 B HBM traffic per input byte vs 3.0
-     * for the kernel pair) */
-    if (sums_dev != nullptr && (algo == MEC_BITROT_HIGHWAYHASH256 ||
-                                algo == MEC_BITROT_HIGHWAYHASH256S)) {
-        FusedArgs fa{};
-        fa.data = (const uint8_t *)data_dev;
-        fa.parity = (uint8_t *)parity_dev;
-        fa.sums = (uint8_t *)sums_dev;
-        fa.row_stride = ctx->stride;
-        fa.shard_len = S_call;
-        fa.n = n;
-        memcpy(fa.key, kMagicHHKey, 32);
-        hipError_t he = mec_launch_fused3_encode_hh(d, p, &fa, ctx->stream);
-        if (he == hipSuccess) return MEC_OK;
-        if (he != hipErrorNotSupported) {
-            set_err("fused3_encode_hh", he);
-            return MEC_ERR_HIP;
-        }
-        he = mec_launch_fused2_encode_hh(d, p, &fa, ctx->stream);
-        if (he == hipSuccess) return MEC_OK;
-        if (he != hipErrorNotSupported) {
-            set_err("fused2_encode_hh", he);
-            return MEC_ERR_HIP;
-        }
-        he = mec_launch_fused_encode_hh(d, p, &fa, ctx->stream);
-        if (he == hipSuccess) return MEC_OK;
-        if (he != hipErrorNotSupported) {
-            set_err("fused_encode_hh", he);
-            return MEC_ERR_HIP;
-        }
-        if (f4_takes(ctx, n)) {
-            he = mec_launch_fused4_encode_hh(d, p, &fa, ctx->stream);
-            if (he == hipSuccess) return MEC_OK;
-            if (he != hipErrorNotSupported) {
-                set_err("fused4_encode_hh", he);
-                return MEC_ERR_HIP;
-            }
+    if (sums_dev != nullptr) {
+        switch (try_fused4(ctx, n, data_dev, S_call, parity_dev, algo,
+                           sums_dev)) {
+        case F4::Launched: return MEC_OK;
+        case F4::Error: return MEC_ERR_HIP;
+        case F4::NotTaken: break;
         }
     }
     /* specialized straight-line kernel for common geometries */
-    {
-        GfEncArgs ea{};
-        ea.data = (const uint8_t *)data_dev;
-        ea.parity = (uint8_t *)parity_dev;
-        ea.row_stride = ctx->stride;
-        ea.shard_len = S_call;
-        hipError_t he =
-            mec_launch_gf_encode_spec(d, p, &ea, n, ctx->stream);
-        if (he == hipSuccess) goto gf_done;
-        if (he != hipErrorNotSupported) {
-            set_err("gf_encode_spec", he);
-            return MEC_ERR_HIP;
-        }
+    GfEncArgs ea{};
+    ea.data = (const uint8_t *)data_dev;
+    ea.parity = (uint8_t *)parity_dev;
+    ea.row_stride = ctx->stride;
+    ea.shard_len = S_call;
+    const hipError_t he_spec =
+        mec_launch_gf_encode_spec(d, p, &ea, n, ctx->stream);
+    if (he_spec != hipSuccess && he_spec != hipErrorNotSupported) {
+        set_err("gf_encode_spec", he_spec);
+        return MEC_ERR_HIP;
     }
-    /* generic fallback: GF parity rows, in groups of <= MEC_KMAX_E */
-    for (int i0 = 0; i0 < p; i0 += MEC_KMAX_E) {
-        int e = p - i0 > MEC_KMAX_E ? MEC_KMAX_E : p - i0;
-        GfMatmulArgs a{};
-        a.src = (const uint8_t *)data_dev;
-        a.dst = (uint8_t *)parity_dev;
-        a.src_item_stride = (int64_t)d * ctx->stride;
-        a.dst_item_stride = (int64_t)p * ctx->stride;
-        a.row_stride = ctx->stride;
-        a.shard_len = S_call;
-        a.d = d;
-        for (int k = 0; k < d; k++) a.src_rows[k] = (uint8_t)k;
-        for (int i = 0; i < e; i++) a.dst_rows[i] = (uint8_t)(i0 + i);
-        for (int i = 0; i < e; i++)
-            for (int k = 0; k < d; k++)
-                a.mat[i * MEC_KMAX_D + k] =
-                    ctx->enc_matrix[(size_t)(d + i0 + i) * d + k];
-        {
-            uint32_t masks[MEC_KMAX_E * MEC_KMAX_D * 2];
-            for (int i = 0; i < e; i++)
-                for (int k = 0; k < d; k++)
-                    bs_pack_matrix(a.mat[i * MEC_KMAX_D + k],
-                                   &masks[((size_t)i * d + k) * 2]);
-            size_t mw = (size_t)e * d * 2;
-            size_t mb = mw * sizeof(uint32_t);
-            if (ctx->m_cached.size() != mw ||
-                memcmp(ctx->m_cached.data(), masks, mb) != 0) {
-                mec_status st2;
-                if ((st2 = ctx->ensure(&ctx->dev_m, &ctx->cap_m, mb)) !=
-                    MEC_OK)
-                    return st2;
-                /* prior launches may still read dev_m */
-                HIP_TRY(hipStreamSynchronize(ctx->stream));
-                HIP_TRY(hipMemcpy(ctx->dev_m, masks, mb,
-                                  hipMemcpyHostToDevice));
-                ctx->m_cached.assign(masks, masks + mw);
-            }
-            a.bs_masks = (const uint32_t *)ctx->dev_m;
-        }
-        HIP_TRY(mec_launch_gf_matmul(&a, e, n, ctx->stream));
+    if (he_spec == hipErrorNotSupported) {
+        mec_status st = encode_generic(ctx, n, data_dev, S_call, parity_dev);
+        if (st != MEC_OK) return st;
     }
-gf_done:
     if (sums_dev != nullptr) {
         if (!hash_size(algo)) return MEC_ERR_INVALID_ARG;
         /* single launch with every chain in flight: the hash is
@@ -482,18 +463,8 @@ gf_done:
          * the GF kernel's 8-waves/SIMD occupancy) measurably regresses —
          * measured: overlapped split 2.04 ms/step vs sequential
          * single-launch 1.12 ms/step at EC8+4/1MiB/1024. */
-        HashArgs h{};
-        h.data = (const uint8_t *)data_dev;
-        h.parity = (const uint8_t *)parity_dev;
-        h.sums = (uint8_t *)sums_dev;
-        h.row_stride = ctx->stride;
-        h.msg_len = S_call;
-        h.d = d;
-        h.p = p;
-        h.mode = MEC_HASH_ALL;
-        h.n_chains = (int64_t)n * (d + p);
-        memcpy(h.key, kMagicHHKey, 32);
-        HIP_TRY(mec_launch_hash(algo, &h, ctx->stream));
+        return hash_all_rows(ctx, n, data_dev, S_call, parity_dev, algo,
+                             sums_dev, ctx->stream);
     }
     return MEC_OK;
 }
@@ -521,40 +492,16 @@ mec_status mec_encode_batch_dev_pipe(mec_ctx *ctx, int n,
     /* this buffer slot's previous hash must be drained before GF rewrites
      * the parity buffer */
     HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_pipe[idx], 0));
-    /* single-pass fused kernel (r2 default): one launch does GF + hash at
-     * 1.5 B/input byte — cross-batch pipelining degenerates to back-to-
-     * back fused launches, which is what we want (the fused kernel is
-     * memory-bound; overlapping two of them cannot beat sequential) */
-    if (algo == MEC_BITROT_HIGHWAYHASH256 ||
-        algo == MEC_BITROT_HIGHWAYHASH256S) {
-        FusedArgs fa{};
-        fa.data = (const uint8_t *)data_dev;
-        fa.parity = (uint8_t *)parity_dev;
-        fa.sums = (uint8_t *)sums_dev;
-        fa.row_stride = ctx->stride;
-        fa.shard_len = S_call;
-        fa.n = n;
-        memcpy(fa.key, kMagicHHKey, 32);
-        hipError_t he = mec_launch_fused3_encode_hh(d, p, &fa, ctx->stream);
-        if (he == hipSuccess) {
-            HIP_TRY(hipEventRecord(ctx->ev_pipe[idx], ctx->stream));
-            return MEC_OK;
-        }
-        if (he != hipErrorNotSupported) {
-            set_err("fused3_encode_hh", he);
-            return MEC_ERR_HIP;
-        }
-        if (f4_takes(ctx, n)) {
-            he = mec_launch_fused4_encode_hh(d, p, &fa, ctx->stream);
-            if (he == hipSuccess) {
-                HIP_TRY(hipEventRecord(ctx->ev_pipe[idx], ctx->stream));
-                return MEC_OK;
-            }
-            if (he != hipErrorNotSupported) {
-                set_err("fused4_encode_hh", he);
-                return MEC_ERR_HIP;
-            }
-        }
+    /* one-pass kernel: one launch does GF + hash at 1.5 B/input byte —
+     * cross-batch pipelining degenerates to back-to-back fused launches,
+     * which is what we want (the fused kernel is memory-bound; overlapping
+     * two of them cannot beat sequential) */
+    switch (try_fused4(ctx, n, data_dev, S_call, parity_dev, algo, sums_dev)) {
+    case F4::Launched:
+        HIP_TRY(hipEventRecord(ctx->ev_pipe[idx], ctx->stream));
+        return MEC_OK;
+    case F4::Error: return MEC_ERR_HIP;
+    case F4::NotTaken: break;
     }
     {
         GfEncArgs ea{};
@@ -572,20 +519,9 @@ mec_status mec_encode_batch_dev_pipe(mec_ctx *ctx, int n,
     }
     HIP_TRY(hipEventRecord(ctx->ev_gf, ctx->stream));
     HIP_TRY(hipStreamWaitEvent(ctx->stream2, ctx->ev_gf, 0));
-    {
-        HashArgs h{};
-        h.data = (const uint8_t *)data_dev;
-        h.parity = (const uint8_t *)parity_dev;
-        h.sums = (uint8_t *)sums_dev;
-        h.row_stride = ctx->stride;
-        h.msg_len = S_call;
-        h.d = d;
-        h.p = p;
-        h.mode = MEC_HASH_ALL;
-        h.n_chains = (int64_t)n * (d + p);
-        memcpy(h.key, kMagicHHKey, 32);
-        HIP_TRY(mec_launch_hash(algo, &h, ctx->stream2));
-    }
+    mec_status st = hash_all_rows(ctx, n, data_dev, S_call, parity_dev, algo,
+                                  sums_dev, ctx->stream2);
+    if (st != MEC_OK) return st;
     HIP_TRY(hipEventRecord(ctx->ev_pipe[idx], ctx->stream2));
     return MEC_OK;
 }
@@ -923,30 +859,8 @@ static mec_status reconstruct_dev_locked(mec_ctx *ctx, int n,
         for (int i = 0; i < e; i++)
             for (int k = 0; k < d; k++)
                 a.mat[i * MEC_KMAX_D + k] = dec[(size_t)(t0 + i) * d + k];
-        /* bit-sliced path: pack the 8x8 bit matrices and upload (a few
-         * hundred bytes; synchronous — tiny next to the kernel) */
-        {
-            uint32_t masks[MEC_KMAX_E * MEC_KMAX_D * 2];
-            for (int i = 0; i < e; i++)
-                for (int k = 0; k < d; k++)
-                    bs_pack_matrix(a.mat[i * MEC_KMAX_D + k],
-                                   &masks[((size_t)i * d + k) * 2]);
-            size_t mw = (size_t)e * d * 2;
-            size_t mb = mw * sizeof(uint32_t);
-            if (ctx->m_cached.size() != mw ||
-                memcmp(ctx->m_cached.data(), masks, mb) != 0) {
-                mec_status st2;
-                if ((st2 = ctx->ensure(&ctx->dev_m, &ctx->cap_m, mb)) !=
-                    MEC_OK)
-                    return st2;
-                /* prior launches may still read dev_m */
-                HIP_TRY(hipStreamSynchronize(ctx->stream));
-                HIP_TRY(hipMemcpy(ctx->dev_m, masks, mb,
-                                  hipMemcpyHostToDevice));
-                ctx->m_cached.assign(masks, masks + mw);
-            }
-            a.bs_masks = (const uint32_t *)ctx->dev_m;
-        }
+        mec_status st = bs_masks_dev(ctx, a.mat, e, d, &a.bs_masks);
+        if (st != MEC_OK) return st;
         HIP_TRY(mec_launch_gf_matmul(&a, e, n, ctx->stream));
     }
     return MEC_OK;

@@ -2,12 +2,13 @@
  * is fetched from HBM exactly once.
  *
  * Semantics of cmd/erasure-coding.go:85 (GF parity) +
- * cmd/bitrot-streaming.go:57-59 (per-shard HH256) in ONE launch, like
- * fused/fused2/fused3 — what differs is how the bytes travel:
+ * cmd/bitrot-streaming.go:57-59 (per-shard HH256) in ONE launch.  Three
+ * earlier one-launch kernels were measured slower than the kernel pair and
+ * are retired; what differs here is how the bytes travel:
  *
  *  - a LOADER wave streams the data rows of the workgroup's G blocks into
  *    an LDS ring with global_load_lds_dwordx4 (no VGPR, no ds_write: the
- *    ds_write_b128 issue cost is what sank fused2 and the first fused3),
+ *    ds_write_b128 issue cost is what sank the earlier LDS-ring attempts),
  *    one T-byte tile of every row per step, LA tiles ahead;
  *  - NGF GF waves read 32-B columns from that ring, run the bit-sliced
  *    transpose / fold / transpose of gf_bs.h, and write parity twice: to
@@ -17,7 +18,7 @@
  *    code, only the per-lane base and the lag differ.
  *
  * HBM traffic: data 1x read + parity 1x write = 1.5 B per input byte (the
- * kernel pair moves 3.0, fused3 2.5).
+ * kernel pair moves 3.0).
  *
  * Synchronisation is deliberately dumb.  Every wave of the workgroup
  * executes exactly 1 + NS barriers, NS = shard_len/T + NGF, a number that
@@ -51,14 +52,11 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdlib>
-#include <cstring>
 
 #include "kernels.h"
 #include "ec_matrices_gen.h"
 #include "gf_bs.h"
 #include "hh_quad.h"
-
-extern char **environ;
 
 namespace fused4 {
 
@@ -321,17 +319,12 @@ fused4_encode_hh_kernel(FusedArgs a) {
     }
 }
 
-/* 1 unless MEC_FUSED4=0 or an encode experiment knob is in the
- * environment: those select the kernels they were written for. */
+/* MEC_FUSED4, if set, decides.  Otherwise fused4 is off exactly when
+ * MEC_PIPE is in the environment (whatever its value): that knob asks for
+ * the kernel pair, whose cross-batch pipelining it switches. */
 static bool fused4_env_enabled() {
     if (const char *v = getenv("MEC_FUSED4")) return atoi(v) != 0;
-    static const char *const knobs[] = {"MEC_FUSED",  "MEC_F3_",   "MEC_HH4",
-                                        "MEC_HH_WG",  "MEC_HH4_WG", "MEC_HH_LDS",
-                                        "MEC_GF_",    "MEC_PIPE"};
-    for (char **e = environ; e && *e; e++)
-        for (const char *k : knobs)
-            if (strncmp(*e, k, strlen(k)) == 0) return false;
-    return true;
+    return getenv("MEC_PIPE") == nullptr;
 }
 
 static std::atomic<uint64_t> g_fused4_launches{0};

@@ -1,6 +1,6 @@
-/* Bit-sliced GF(2^8) device helpers shared by the standalone encode
- * kernel (kernels.hip) and the fused producer (fused3.hip).  See
- * gf_encode_bs_kernel's comment for the design and measured numbers. */
+/* Bit-sliced GF(2^8) device helpers shared by the standalone encode and
+ * matmul kernels (kernels.hip, encode_var.hip, recon_mixed.hip) and the GF
+ * waves of the one-pass kernel (fused4.hip). */
 #ifndef MEC_GF_BS_H
 #define MEC_GF_BS_H
 #include <hip/hip_runtime.h>
@@ -8,7 +8,8 @@
 
 /* ---- bit-sliced specialized encode (r2) --------------------------------
  *
- * The SWAR xtime ladder costs ~1.46 VALU per input byte (and the int-VALU
+ * The SWAR xtime ladder this replaced (r1; retired) costs
+ * ~1.46 VALU per input byte (and the int-VALU
  * pipe measures ~4 cyc/instr on gfx950, making the GF leg VALU-PIPE-bound
  * at ~0.32 ms for the headline batch — r2 SQ counters).  Bit-slicing cuts
  * the instruction count ~2.4x: each lane takes a 32-byte column per row,

@@ -1,8 +1,7 @@
 /* HighwayHash-256 at 4 GPU lanes per chain: the per-lane state and packet
  * update shared by hh256_batch4_kernel (kernels.hip) and the list-driven
- * kernels (hh_list.hip).  Device code only; why 4 lanes per chain, and the
- * byte layout behind the v_perm selectors: see the comments above
- * zip_even/zip_odd and hh256_batch4_kernel in kernels.hip. */
+ * kernels (hh_list.hip).  Device code only; why 4 lanes per chain: see the
+ * comment above hh256_batch4_kernel in kernels.hip. */
 #ifndef MEC_HH_QUAD_H
 #define MEC_HH_QUAD_H
 
@@ -27,8 +26,18 @@ struct HH1 {
     uint64_t v0, v1, mul0, mul1; /* this lane's single HighwayHash lane */
 };
 
-/* One packet update for HH lane j (lane parity selects the zipper hi
- * selector; S1/S2 are parity-independent — see zip_even/zip_odd, kernels.hip). */
+/* One packet update for HH lane j.
+ *
+ * The zipper merge is a pure byte permutation of a lane pair (the reference
+ * implements it with pshufb); on CDNA4 that is v_perm_b32: 3 perms + 1 or
+ * per output word instead of a ~17-op shift/mask tree.  With A = the even
+ * lane's word and B = the odd lane's word of the pair:
+ *   even lane out bytes (LSB..MSB): [A3 B4 A2 A5 | B6 A1 B7 A0]
+ *   odd lane out bytes:             [B3 A4 B2 B5 | B1 A6 B0 A7]
+ * v_perm pool = {hi:lo}, selector byte 12 yields 0x00.  Seen from either
+ * lane the low word takes the same bytes of (own, partner's high word), so
+ * its two selectors are parity-independent; only the high word's selector
+ * S3 depends on lane parity (0x00070106 even, 0x07000601 odd). */
 __device__ __forceinline__ void hh1_update(HH1 &s, uint64_t w, uint32_t S3) {
     s.v1 += s.mul0 + w;
     s.mul0 ^= (s.v1 & 0xffffffffull) * (s.v0 >> 32);

@@ -27,7 +27,7 @@ struct GfMatmulArgs {
     /* bit-sliced path (r2): device pointer to E*d*2 u32 —
      * bs_masks[(t*d+k)*2 + w] = dword w of the 8x8 bit matrix of
      * mat[t][k] (byte b = rowmask(c,b): bit a set iff output bit b of
-     * c*x depends on input bit a).  NULL -> ladder kernel. */
+     * c*x depends on input bit a).  Required: NULL is refused. */
     const uint32_t *bs_masks;
 };
 
@@ -105,7 +105,7 @@ struct EncVarArgs {
     uint64_t key[4];
 };
 
-/* Fused single-pass encode+HighwayHash (fused.hip) */
+/* Fused single-pass encode+HighwayHash (fused4.hip) */
 struct FusedArgs {
     const uint8_t *data; /* n * d * row_stride */
     uint8_t *parity;     /* n * p * row_stride (output) */
@@ -114,9 +114,9 @@ struct FusedArgs {
     int64_t shard_len;
     int64_t n;
     uint64_t key[4];
-    int probe; /* 0 normal; perf-isolation probes (results INVALID):
-                  1 producers only, 2 consumers free-run (no poll),
-                  3 both free-run */
+    int probe; /* 0 normal; perf-isolation bits (results INVALID), set by
+                  the launcher from MEC_F4_PROBE: 1 hash waves idle,
+                  2 GF waves idle, 4 loader issues nothing */
 };
 
 struct ScatterArgs {
@@ -145,12 +145,6 @@ hipError_t mec_launch_scatter_rows(const ScatterArgs *args,
                                    hipStream_t stream);
 hipError_t mec_launch_stream_interleave(const InterleaveArgs *args,
                                         hipStream_t stream);
-hipError_t mec_launch_fused_encode_hh(int d, int p, const FusedArgs *args,
-                                      hipStream_t stream);
-hipError_t mec_launch_fused3_encode_hh(int d, int p, const FusedArgs *args,
-                                       hipStream_t stream);
-hipError_t mec_launch_fused2_encode_hh(int d, int p, const FusedArgs *args,
-                                       hipStream_t stream);
 /* one-pass kernel of fused4.hip; hipErrorNotSupported, with nothing
  * launched, when the shape is not eligible or a knob turns it off */
 hipError_t mec_launch_fused4_encode_hh(int d, int p, const FusedArgs *args,

@@ -555,7 +555,7 @@ def test_empty_object_paths():
         assert wsums[0] == oracle.bitrot_sum(oracle.SHA256, b"")
 
 
-# ---- off-default experiment knobs (env-latched -> subprocess) -----------
+# ---- live and retired knobs (env-latched -> subprocess) -----------------
 
 _KNOB_CHECK = r"""
 import os, sys
@@ -592,46 +592,60 @@ print("KNOB_OK")
 """
 
 
-@pytest.mark.parametrize("knob", ["MEC_HH_LDS", "MEC_FUSED2", "MEC_FUSED",
-                                  "MEC_FUSED3",
-                                  "MEC_HH_WG", "MEC_HH4_OFF", "MEC_SHA_WG",
-                                  "MEC_FUSED3_OFF", "MEC_F3_MIN1",
-                                  "MEC_F3_MIN1_W4", "MEC_F3_MIN1_W6",
-                                  "MEC_GF_BS_OFF"])
+# Run after _KNOB_CHECK in the same process when a retired knob is set: the
+# knob must be ignored.  Until commit 762fd47 the presence of an encode
+# experiment knob silently sent every batch to the kernel pair; now an
+# eligible batch (MEC_F4_MIN is read per context) must still take the one-pass
+# kernel, once, and match both the oracle and the pair
+# (test_gpu_fused4.encode_case asserts all three).
+_KNOB_IGNORED_CHECK = r"""
+sys.path.insert(0, os.path.join(os.environ["MEC_TEST_REPO"], "tests"))
+os.environ["MEC_F4_MIN"] = "1"
+import test_gpu_fused4 as t
+t.encode_case(5, t.DP * t.T, t.D * t.DP * t.T, True)
+print("KNOB_IGNORED_OK")
+"""
+
+# Retired knobs (DESIGN.md §9), one per deleted kernel family, with the value
+# that used to select the experiment.  The library no longer reads them.
+_RETIRED_KNOBS = {
+    "MEC_HH_LDS": {"MEC_HH_LDS": "1"},
+    "MEC_FUSED2": {"MEC_FUSED2": "1"},
+    "MEC_FUSED": {"MEC_FUSED": "1"},
+    "MEC_FUSED3": {"MEC_FUSED3": "1"},
+    "MEC_HH_WG": {"MEC_HH_WG": "512"},
+    "MEC_HH4_OFF": {"MEC_HH4": "0"},
+    "MEC_SHA_WG": {"MEC_SHA_WG": "512"},
+    "MEC_GF_BS_OFF": {"MEC_GF_BS": "0"},
+}
+
+
+@pytest.mark.parametrize("knob", ["default", "MEC_FUSED4=0",
+                                  *_RETIRED_KNOBS])
 def test_knob_variants_bit_exact(knob):
-    """The in-tree experiment knobs are env-latched at first
-    use, so each variant runs in a subprocess.  Every knob'd kernel must
-    stay bit-exact vs the oracle (covers the MEC_HH_LDS hand-placed
-    s_waitcnt double-buffer handoff, which no default-path test reaches)."""
+    """Knobs are env-latched at first use, so each setting runs in a
+    subprocess, started with every MEC_* variable removed: `default` adds
+    nothing (what a caller gets: the library's own choice between the
+    one-pass kernel and the kernel pair), `MEC_FUSED4=0` takes the kernel
+    pair everywhere, and each retired knob is set to the value that used to
+    select its experiment.  Every run must be bit-exact vs the oracle, the
+    ragged HighwayHash and the SHA launches included; under a retired knob
+    the one-pass kernel must in addition still take an eligible batch
+    (_KNOB_IGNORED_CHECK), which it did not while the knob was read."""
     import subprocess
-    env = dict(os.environ)
-    if knob in ("MEC_HH_WG", "MEC_SHA_WG"):
-        env[knob] = "512"
-    elif knob == "MEC_HH4_OFF":
-        env["MEC_HH4"] = "0"   # the r1 pair-lane kernel
-    elif knob == "MEC_FUSED3_OFF":
-        env["MEC_FUSED3"] = "0"  # two-kernel pair instead of fused v3
-    elif knob == "MEC_F3_MIN1":
-        env["MEC_FUSED3"] = "1"
-        env["MEC_F3_MIN"] = "1"  # force fused3 8-wave at ANY batch size
-        env["MEC_F3_CFG"] = "8"
-    elif knob == "MEC_F3_MIN1_W4":
-        env["MEC_FUSED3"] = "1"
-        env["MEC_F3_MIN"] = "1"  # force fused3 4-wave at ANY batch size
-        env["MEC_F3_CFG"] = "4"
-    elif knob == "MEC_F3_MIN1_W6":
-        env["MEC_FUSED3"] = "1"
-        env["MEC_F3_MIN"] = "1"  # force fused3 6-wave (bit-sliced producer)
-        env["MEC_F3_CFG"] = "6"
-    elif knob == "MEC_GF_BS_OFF":
-        env["MEC_GF_BS"] = "0"   # xtime-ladder encode kernel
-    else:
-        env[knob] = "1"
+    env = {k: v for k, v in os.environ.items() if not k.startswith("MEC_")}
+    script, marks = _KNOB_CHECK, ["KNOB_OK"]
+    if knob in _RETIRED_KNOBS:
+        env.update(_RETIRED_KNOBS[knob])
+        script += _KNOB_IGNORED_CHECK
+        marks.append("KNOB_IGNORED_OK")
+    elif knob != "default":
+        name, value = knob.split("=")
+        env[name] = value
     env["MEC_TEST_REPO"] = os.path.dirname(HERE)
-    r = subprocess.run([os.environ.get("PYTHON", "python3"), "-c",
-                        _KNOB_CHECK], env=env, capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0 and "KNOB_OK" in r.stdout, (
+    r = subprocess.run([os.environ.get("PYTHON", "python3"), "-c", script],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and all(m in r.stdout for m in marks), (
         knob, r.returncode, r.stdout[-2000:], r.stderr[-2000:])
 
 
