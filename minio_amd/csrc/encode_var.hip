@@ -15,7 +15,7 @@
  *
  * Per-lane math is the uniform kernels', unchanged: gf_encode_bs_kernel
  * (kernels.hip, helpers in gf_bs.h) and the 4-lanes-per-chain HighwayHash
- * of hh256_list_body (hh_list.hip, helpers in hh_quad.h).
+ * of hh_quad.h.
  */
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -139,18 +139,15 @@ __global__ void __launch_bounds__(256) gf_encode_bs_var_kernel(EncVarArgs a) {
     }
 }
 
-/* hh256_list_body's chain in sum mode (4 lanes per chain, quad DPP,
- * 16-packet double buffer) with the message length and the row pointer per
- * chain: slot = tid >> 2 names row slot % (d+p) of item
- * order[slot / (d+p)], read from the data or the parity buffer over exactly
- * S_i bytes; its digest goes to the fused slot (item*(d+p)+row)*32.
+/* hh_quad.h's chain with the message length and the row pointer per chain:
+ * slot = tid >> 2 names row slot % (d+p) of item order[slot / (d+p)], read
+ * from the data or the parity buffer over exactly S_i bytes; its digest
+ * goes to the fused slot (item*(d+p)+row)*32.
  *
- * The DPP swaps take values from lanes of the same quad, and a partly
- * active quad reads zeros (bound_ctrl) and yields a wrong digest with no
- * fault.  So every loop trip, branch and return below depends on the chain
- * alone (slot, len): the four lanes of a chain take them together.  Waves
- * do diverge between chains of different lengths; the descending order
- * keeps the 16 chains of a wave near-equal. */
+ * The quad contract holds with per-chain lengths because the return, len
+ * and the tail branch below depend on the chain alone (slot, S), never on
+ * j.  Waves do diverge between chains of different lengths; the descending
+ * order keeps the 16 chains of a wave near-equal. */
 __global__ void __launch_bounds__(256) hh256_var_kernel(EncVarArgs a) {
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t slot = tid >> 2;
@@ -170,122 +167,15 @@ __global__ void __launch_bounds__(256) hh256_var_kernel(EncVarArgs a) {
              : a.parity + (int64_t)a.p * R +
                    (int64_t)(srow - (uint32_t)a.d) * row_stride) +
         8 * j;
-    const uint32_t S3 = (j & 1) ? 0x07000601u : 0x00070106u;
+    const uint32_t S3 = hh1_sel(j);
 
-    const uint64_t init0[4] = {0xdbe6d5d5fe4cce2full, 0xa4093822299f31d0ull,
-                               0x13198a2e03707344ull, 0x243f6a8885a308d3ull};
-    const uint64_t init1[4] = {0x3bd39e10cb0ef593ull, 0xc0acf169b5f18a8cull,
-                               0xbe5466cf34e90c6cull, 0x452821e638d01377ull};
     HH1 s;
-    s.mul0 = init0[j];
-    s.mul1 = init1[j];
-    s.v0 = init0[j] ^ a.key[j];
-    s.v1 = init1[j] ^ ((a.key[j] >> 32) | (a.key[j] << 32));
-
+    hh1_init(s, a.key, j);
     int64_t len = S;
-    constexpr int DP = 16; /* prefetch depth (packets); 8 B each */
-    uint64_t qa[DP], qb[DP];
-#define HHV_LOAD(Q)                                                          \
-    {                                                                        \
-        _Pragma("unroll") for (int t = 0; t < DP; t++)                       \
-            Q[t] = *(const uint64_t *)(mp + 32 * t);                         \
-        mp += 32 * DP;                                                       \
-    }
-#define HHV_COMP(Q)                                                          \
-    {                                                                        \
-        _Pragma("unroll") for (int t = 0; t < DP; t++)                       \
-            hh1_update(s, Q[t], S3);                                         \
-    }
-    __builtin_amdgcn_s_setprio(1);
-    if (len >= 32 * DP) {
-        HHV_LOAD(qa)
-        len -= 32 * DP;
-        while (len >= 2 * 32 * DP) {
-            HHV_LOAD(qb)
-            HHV_COMP(qa)
-            HHV_LOAD(qa)
-            HHV_COMP(qb)
-            len -= 2 * 32 * DP;
-        }
-        if (len >= 32 * DP) {
-            HHV_LOAD(qb)
-            HHV_COMP(qa)
-            HHV_COMP(qb)
-            len -= 32 * DP;
-        } else {
-            HHV_COMP(qa)
-        }
-    }
-#undef HHV_LOAD
-#undef HHV_COMP
-    __builtin_amdgcn_s_setprio(0);
-    while (len >= 32) {
-        uint64_t w = *(const uint64_t *)mp;
-        hh1_update(s, w, S3);
-        mp += 32;
-        len -= 32;
-    }
-    if (len > 0) {
-        /* UpdateRemainder.  The padded 32-byte packet is
-         *   [0, mod32 & ~3)      the tail's whole dwords,
-         *   mod32 & 16:  [28,32) the tail's last 4 bytes,
-         *   else mod4:   16,17,18 = rem[0], rem[mod4>>1], rem[mod4-1],
-         *   zero elsewhere;
-         * each lane fetches only the 8 bytes of its own word, so there is
-         * no per-lane packet array */
-        const int mod32 = (int)len;
-        const int mod4 = mod32 & 3;
-        const int whole = mod32 & ~3;
-        const uint8_t *tail_msg = mp - 8 * j;
-        s.v0 += ((uint64_t)mod32 << 32) + (uint64_t)mod32;
-        {
-            uint32_t h0 = (uint32_t)s.v1;
-            uint32_t h1 = (uint32_t)(s.v1 >> 32);
-            s.v1 = (uint32_t)((h0 << mod32) | (h0 >> (32 - mod32)));
-            s.v1 |= (uint64_t)((h1 << mod32) | (h1 >> (32 - mod32))) << 32;
-        }
-        uint64_t w = 0;
-#pragma unroll
-        for (int bt = 7; bt >= 0; bt--) {
-            const int q = 8 * j + bt; /* byte of the packet */
-            int src = -1;             /* byte of the tail, -1: zero */
-            if (q < whole)
-                src = q;
-            else if (mod32 & 16) {
-                if (q >= 28) src = mod32 - 32 + q;
-            } else if (mod4) {
-                if (q == 16) src = whole;
-                if (q == 17) src = whole + (mod4 >> 1);
-                if (q == 18) src = whole + mod4 - 1;
-            }
-            /* tail_msg[0] is a message byte (len > 0): load, then select */
-            const uint32_t b = tail_msg[src < 0 ? 0 : src];
-            w = (w << 8) | (src < 0 ? 0u : b);
-        }
-        hh1_update(s, w, S3);
-    }
-    /* 10 permute-update rounds: permuted[j] = rot32(v0[j ^ 2]) */
-#pragma unroll 1
-    for (int r = 0; r < 10; r++) {
-        uint32_t p_lo = dpp_swap2((uint32_t)s.v0);
-        uint32_t p_hi = dpp_swap2((uint32_t)(s.v0 >> 32));
-        hh1_update(s, ((uint64_t)p_lo << 32) | p_hi, S3);
-    }
-    /* modular reduction, as in hh256_list_body: lane j ends up with digest
-     * word j */
-    uint64_t t = s.v0 + s.mul0;
-    uint64_t sv = s.v1 + s.mul1;
-    uint32_t se_lo = dpp_swap1((uint32_t)sv);
-    uint32_t se_hi = dpp_swap1((uint32_t)(sv >> 32));
-    uint64_t se = ((uint64_t)se_hi << 32) | se_lo; /* partner's s */
-    uint64_t out;
-    if ((j & 1) == 0) {
-        out = t ^ (sv << 1) ^ (sv << 2);
-    } else {
-        uint64_t a3 = sv & 0x3fffffffffffffffull;
-        out = t ^ ((a3 << 1) | (se >> 63)) ^ ((a3 << 2) | (se >> 62));
-    }
-    *(uint64_t *)(a.sums + (item * total + srow) * 32 + 8 * j) = out;
+    HH1_STREAM(s, mp, len, S3)
+    if (len > 0) hh1_remainder(s, mp, (int)len, j, S3);
+    *(uint64_t *)(a.sums + (item * total + srow) * 32 + 8 * j) =
+        hh1_finish(s, j, S3);
 }
 
 extern "C" int mec_encode_var_supported(int d, int p) {

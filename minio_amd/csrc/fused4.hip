@@ -245,8 +245,9 @@ fused4_encode_hh_kernel(FusedArgs a) {
         return;
     }
 
-    /* ---- hash waves: 4 lanes per chain (hh256_batch4 shape).  Data
-     * chains hash tile s in step s, parity chains tile s-NGF. ---- */
+    /* ---- hash waves: 4 lanes per chain; init and finish are hh_quad.h's,
+     * the packet loop is paced by the step barriers.  Data chains hash
+     * tile s in step s, parity chains tile s-NGF. ---- */
     const int ln = (wid - 1 - NGF) * 64 + lane;
     const int cp = ln >> 2; /* chain index in the workgroup */
     const int j = ln & 3;   /* HighwayHash lane */
@@ -258,25 +259,12 @@ fused4_encode_hh_kernel(FusedArgs a) {
     const int lag = isp ? NGF : 0;
     const int rr = 32 * (row & 15) + 8 * j;
     const int rbase = (isp ? PBASE : 0) + row * T;
-    const uint32_t S3 = (j & 1) ? 0x07000601u : 0x00070106u;
+    const uint32_t S3 = hh1_sel(j);
 
     __builtin_amdgcn_s_setprio(1);
 
     HH1 st;
-    {
-        const uint64_t init0[4] = {0xdbe6d5d5fe4cce2full,
-                                   0xa4093822299f31d0ull,
-                                   0x13198a2e03707344ull,
-                                   0x243f6a8885a308d3ull};
-        const uint64_t init1[4] = {0x3bd39e10cb0ef593ull,
-                                   0xc0acf169b5f18a8cull,
-                                   0xbe5466cf34e90c6cull,
-                                   0x452821e638d01377ull};
-        st.mul0 = init0[j];
-        st.mul1 = init1[j];
-        st.v0 = init0[j] ^ a.key[j];
-        st.v1 = init1[j] ^ ((a.key[j] >> 32) | (a.key[j] << 32));
-    }
+    hh1_init(st, a.key, j);
 
     step_barrier(); /* prologue */
     for (int64_t s = 0; s < NS; s++) {
@@ -295,28 +283,10 @@ fused4_encode_hh_kernel(FusedArgs a) {
     }
     __builtin_amdgcn_s_setprio(0);
 
-    /* finalise + store sums (hh256_batch4 epilogue) */
-    if (act) {
-#pragma unroll 1
-        for (int r = 0; r < 10; r++) {
-            uint32_t p_lo = dpp_swap2((uint32_t)st.v0);
-            uint32_t p_hi = dpp_swap2((uint32_t)(st.v0 >> 32));
-            hh1_update(st, ((uint64_t)p_lo << 32) | p_hi, S3);
-        }
-        uint64_t t = st.v0 + st.mul0;
-        uint64_t sv = st.v1 + st.mul1;
-        uint32_t se_lo = dpp_swap1((uint32_t)sv);
-        uint32_t se_hi = dpp_swap1((uint32_t)(sv >> 32));
-        uint64_t se = ((uint64_t)se_hi << 32) | se_lo;
-        uint64_t out;
-        if ((j & 1) == 0) {
-            out = t ^ (sv << 1) ^ (sv << 2);
-        } else {
-            uint64_t a3 = sv & 0x3fffffffffffffffull;
-            out = t ^ ((a3 << 1) | (se >> 63)) ^ ((a3 << 2) | (se >> 62));
-        }
-        *(uint64_t *)(a.sums + ((b0 + cg) * TOT + cs) * 32 + 8 * j) = out;
-    }
+    /* finalise + store sums */
+    if (act)
+        *(uint64_t *)(a.sums + ((b0 + cg) * TOT + cs) * 32 + 8 * j) =
+            hh1_finish(st, j, S3);
 }
 
 /* MEC_FUSED4, if set, decides.  Otherwise fused4 is off exactly when

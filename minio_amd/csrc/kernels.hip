@@ -28,7 +28,7 @@
 #include <cstdint>
 
 #include "kernels.h"
-#include "hh_quad.h" /* dpp_swap1/2, HH1, hh1_update */
+#include "hh_quad.h" /* the HighwayHash chain, 4 lanes each */
 
 /* gfx950 3-input boolean LUT op (1 full-rate VALU slot) */
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
@@ -260,8 +260,9 @@ __device__ __forceinline__ const uint8_t *chain_ptr(const HashArgs &a,
  *    v_perm selector),
  *  - loads 8 B/lane/packet (dwordx2), same coalescing (a chain's 4 lanes
  *    cover its 32-B packet contiguously).
- * The per-lane state and packet update (dpp_swap1/2, HH1, hh1_update) are
- * in hh_quad.h, shared with the list-driven kernels of hh_list.hip.
+ * The chain itself (init, streaming loop, UpdateRemainder, finish) is
+ * hh_quad.h's, shared by every HighwayHash kernel; this one owns chain_ptr
+ * and the store.
  */
 
 template <bool RAGGED, int WG = 256>
@@ -272,121 +273,14 @@ __global__ void __launch_bounds__(WG) hh256_batch4_kernel(HashArgs a) {
     if (chain >= a.n_chains) return;
     int64_t sum_idx;
     const uint8_t *mp = chain_ptr(a, chain, sum_idx) + 8 * j;
-    const uint32_t S3 = (j & 1) ? 0x07000601u : 0x00070106u;
+    const uint32_t S3 = hh1_sel(j);
 
-    const uint64_t init0[4] = {0xdbe6d5d5fe4cce2full, 0xa4093822299f31d0ull,
-                               0x13198a2e03707344ull, 0x243f6a8885a308d3ull};
-    const uint64_t init1[4] = {0x3bd39e10cb0ef593ull, 0xc0acf169b5f18a8cull,
-                               0xbe5466cf34e90c6cull, 0x452821e638d01377ull};
     HH1 s;
-    s.mul0 = init0[j];
-    s.mul1 = init1[j];
-    s.v0 = init0[j] ^ a.key[j];
-    s.v1 = init1[j] ^ ((a.key[j] >> 32) | (a.key[j] << 32));
-
+    hh1_init(s, a.key, j);
     int64_t len = a.msg_len;
-    constexpr int DP = 16; /* prefetch depth (packets); 8 B each */
-    uint64_t qa[DP], qb[DP];
-#define HH4_LOAD(Q)                                                          \
-    {                                                                        \
-        _Pragma("unroll") for (int t = 0; t < DP; t++)                       \
-            Q[t] = *(const uint64_t *)(mp + 32 * t);                         \
-        mp += 32 * DP;                                                       \
-    }
-#define HH4_COMP(Q)                                                          \
-    {                                                                        \
-        _Pragma("unroll") for (int t = 0; t < DP; t++)                       \
-            hh1_update(s, Q[t], S3);                                         \
-    }
-    __builtin_amdgcn_s_setprio(1);
-    if (len >= 32 * DP) {
-        HH4_LOAD(qa)
-        len -= 32 * DP;
-        while (len >= 2 * 32 * DP) {
-            HH4_LOAD(qb)
-            HH4_COMP(qa)
-            HH4_LOAD(qa)
-            HH4_COMP(qb)
-            len -= 2 * 32 * DP;
-        }
-        if (len >= 32 * DP) {
-            HH4_LOAD(qb)
-            HH4_COMP(qa)
-            HH4_COMP(qb)
-            len -= 32 * DP;
-        } else {
-            HH4_COMP(qa)
-        }
-    }
-#undef HH4_LOAD
-#undef HH4_COMP
-    __builtin_amdgcn_s_setprio(0);
-    while (len >= 32) {
-        uint64_t w = *(const uint64_t *)mp;
-        hh1_update(s, w, S3);
-        mp += 32;
-        len -= 32;
-    }
-    if (RAGGED && len > 0) {
-        /* UpdateRemainder (published portable semantics);
-         * each lane builds the padded 32-B packet privately and consumes
-         * its own 8-B word — tail-only cost */
-        const int mod32 = (int)len;
-        const int mod4 = mod32 & 3;
-        const uint8_t *tail_msg = mp - 8 * j;
-        s.v0 += ((uint64_t)mod32 << 32) + (uint64_t)mod32;
-        {
-            uint32_t h0 = (uint32_t)s.v1;
-            uint32_t h1 = (uint32_t)(s.v1 >> 32);
-            s.v1 = (uint32_t)((h0 << mod32) | (h0 >> (32 - mod32)));
-            s.v1 |= (uint64_t)((h1 << mod32) | (h1 >> (32 - mod32))) << 32;
-        }
-        uint8_t packet[32];
-#pragma unroll
-        for (int i = 0; i < 32; i++) packet[i] = 0;
-        for (int i = 0; i < (mod32 & ~3); i++) packet[i] = tail_msg[i];
-        const uint8_t *rem = tail_msg + (mod32 & ~3);
-        if (mod32 & 16) {
-            for (int i = 0; i < 4; i++)
-                packet[28 + i] = rem[i + mod4 - 4];
-        } else if (mod4) {
-            packet[16] = rem[0];
-            packet[17] = rem[mod4 >> 1];
-            packet[18] = rem[mod4 - 1];
-        }
-        uint64_t w = 0;
-        for (int bt = 7; bt >= 0; bt--) w = (w << 8) | packet[8 * j + bt];
-        hh1_update(s, w, S3);
-    }
-    /* 10 permute-update rounds: permuted[j] = rot32(v0[j ^ 2]) — rot32 of
-     * the cross-pair partner is just its halves swapped */
-#pragma unroll 1
-    for (int r = 0; r < 10; r++) {
-        uint32_t p_lo = dpp_swap2((uint32_t)s.v0);
-        uint32_t p_hi = dpp_swap2((uint32_t)(s.v0 >> 32));
-        hh1_update(s, ((uint64_t)p_lo << 32) | p_hi, S3);
-    }
-    /* modular reduction: lanes {0,1} emit hash[0..1], {2,3} hash[2..3].
-     * m for the pair needs a2 = s0 = partner-even's (v1+mul1):
-     *   even lane j: out = t_j ^ (s_j << 1) ^ (s_j << 2)
-     *   odd lane j:  out = t_j ^ ((s_j' << 1) | (s_e >> 63))
-     *                          ^ ((s_j' << 2) | (s_e >> 62)),
-     *   s_j' = s_j & 0x3fff..., s_e = even partner's s. */
-    {
-        uint64_t t = s.v0 + s.mul0;
-        uint64_t sv = s.v1 + s.mul1;
-        uint32_t se_lo = dpp_swap1((uint32_t)sv);
-        uint32_t se_hi = dpp_swap1((uint32_t)(sv >> 32));
-        uint64_t se = ((uint64_t)se_hi << 32) | se_lo; /* partner's s */
-        uint64_t out;
-        if ((j & 1) == 0) {
-            out = t ^ (sv << 1) ^ (sv << 2);
-        } else {
-            uint64_t a3 = sv & 0x3fffffffffffffffull;
-            out = t ^ ((a3 << 1) | (se >> 63)) ^ ((a3 << 2) | (se >> 62));
-        }
-        *(uint64_t *)(a.sums + sum_idx * 32 + 8 * j) = out;
-    }
+    HH1_STREAM(s, mp, len, S3)
+    if (RAGGED && len > 0) hh1_remainder(s, mp, (int)len, j, S3);
+    *(uint64_t *)(a.sums + sum_idx * 32 + 8 * j) = hh1_finish(s, j, S3);
 }
 
 /* ---- SHA-256 (one chain per lane), FIPS 180-4 -------------------------- */

@@ -115,6 +115,24 @@ def test_bitrot_sum_batch_all_algos_ragged():
                         f"algo={algo} len={mlen} i={i}"
 
 
+def test_bitrot_sum_batch_hh_tail_after_prefetch_block():
+    # 512 bytes are one full 16-packet prefetch block: every mod-32 tail
+    # residue right after it, then the lengths around each edge of the
+    # double-buffered loop (one block, two, three, four)
+    lengths = list(range(512, 544)) + [1023, 1025, 1535, 1536, 1537,
+                                       2047, 2048, 2049]
+    n = 4
+    with minio_amd.Erasure(4, 2, 4096) as e:
+        for mlen in lengths:
+            msgs = rnd(n * mlen, SEED * 5 + mlen)
+            for algo in (minio_amd.HIGHWAYHASH256, minio_amd.HIGHWAYHASH256S):
+                got = e.bitrot_sum_batch(algo, msgs, mlen, mlen, n)
+                for i in range(n):
+                    m = msgs[i * mlen:(i + 1) * mlen]
+                    assert got[i] == oracle.bitrot_sum(algo, m), \
+                        f"hh algo={algo} len={mlen} i={i}"
+
+
 def test_reconstruct_parity_patterns():
     rng = random.Random(7)
     for d, p in [(4, 2), (8, 4), (12, 4), (6, 6)]:

@@ -243,7 +243,9 @@ def test_read_mask_with_holes(extra):
 # ---- 4. lengths that cross every loop edge --------------------------------
 
 LENGTHS = (1, 3, 4, 17, 31, 32, 33, 511, 512, 513, 543, 1024, 1055, 1536,
-           2065, 87382)
+           2065, 87382,
+           # each side of the prefetch loop's edges (blocks of 512 bytes)
+           1023, 1025, 1535, 1537, 2047, 2048, 2049)
 GEOMETRIES = ((2, 1), (4, 2), (8, 4), (12, 4), (16, 4), (8, 8))
 
 
@@ -268,6 +270,31 @@ def test_lengths_cross_every_loop_edge(L, d, p):
     assert st == [0, 0]
     assert (got[:, :, :L] == rows).all()
     assert (got[1] == inp[1]).all()
+
+
+@pytest.mark.parametrize("L", range(512, 544))
+def test_every_tail_residue_after_a_prefetch_block(L):
+    """512 bytes are one full prefetch block, so L covers every mod-32 tail
+    after it.  One row has its last valid byte flipped: verify mode accepts
+    the good rows and rejects that one, and with rehash sum mode writes the
+    rebuilt row's digest."""
+    d, p, n = 4, 2, 2
+    total = d + p
+    rows, sums = golden(d, p, d * L, n, 450 + L)
+    read = np.ones((n, total), dtype=np.uint8)
+    bad = np.zeros((n, total), dtype=bool)
+    with minio_amd.Erasure(d, p, d * L) as e:
+        assert e.shard_size() == L
+        stride = lib.mec_shard_stride(d * L, d)
+        inp, dig = make_input(rows, sums, stride, read)
+        s = L % total
+        flip(inp, 0, s, L - 1, bit=L % 8)   # the last valid byte of one row
+        bad[0, s] = True
+        got, gdig, st = run_and_check(e, oracle.RS(d, p), inp, dig, read, bad,
+                                      L, rehash=1)
+    assert st == [0, 0]
+    assert (got[:, :, :L] == rows).all()
+    assert (gdig == sums).all()
 
 
 # ---- 5. partial waves -----------------------------------------------------
