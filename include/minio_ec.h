@@ -340,7 +340,9 @@ mec_status mec_verify_reconstruct_batch(
 
 /* ---- batch bitrot hash / verify ----------------------------------------
  * msgs: n messages of msg_len bytes at msg_stride; sums: n * hash_size.
- * verify: ok_out[i]=1 where digest matches want[i] (errFileCorrupt map). */
+ * verify: ok_out[i]=1 where digest matches want[i] (errFileCorrupt map).
+ * The _dev entry is tested for msgs_dev 16-byte aligned and msg_stride a
+ * multiple of 16 (SHA-256 and BLAKE2b-512 load 16 bytes at a time). */
 mec_status mec_bitrot_sum_batch_dev(mec_ctx *ctx, int algo, int n,
                                     const void *msgs_dev, int64_t msg_len,
                                     int64_t msg_stride, void *sums_dev);

@@ -736,19 +736,35 @@ static dim3 gf_grid(int64_t shard_len, int grid_scale, int n) {
     return dim3((uint32_t)blocks_x, n);
 }
 
+/* The GF kernels take the batch item from blockIdx.y, and a grid's y
+ * dimension is limited to 65535: a larger batch goes out in slices of at
+ * most that many items, each with its own gf_grid and its base pointers
+ * advanced by the item strides.  Every batch up to the limit is one launch,
+ * as before. */
+constexpr int kMaxGridY = 65535;
+
 extern "C" {
 
 /* Specialized encode launch; returns hipErrorNotSupported when (d,p) has no
  * compiled specialization (caller falls back to the generic kernel). */
 hipError_t mec_launch_gf_encode_spec(int d, int p, const GfEncArgs *args,
                                      int n, hipStream_t stream) {
-    const dim3 grid = gf_grid(args->shard_len, kEncGridScale, n);
 #define X(D, P)                                                              \
     if (d == D && p == P) {                                                  \
-        hipLaunchKernelGGL(                                                  \
-            (gf_encode_bs_kernel<D, P, MAT_##D##_##P, true, kEncPrefetch>),  \
-            grid, dim3(kWg), 0, stream, *args);                              \
-        return hipGetLastError();                                            \
+        for (int b0 = 0; b0 < n; b0 += kMaxGridY) {                          \
+            const int nb = n - b0 < kMaxGridY ? n - b0 : kMaxGridY;          \
+            GfEncArgs sl = *args;                                            \
+            sl.data += (int64_t)b0 * D * args->row_stride;                   \
+            sl.parity += (int64_t)b0 * P * args->row_stride;                 \
+            hipLaunchKernelGGL(                                              \
+                (gf_encode_bs_kernel<D, P, MAT_##D##_##P, true,              \
+                                     kEncPrefetch>),                         \
+                gf_grid(args->shard_len, kEncGridScale, nb), dim3(kWg), 0,   \
+                stream, sl);                                                 \
+            const hipError_t e = hipGetLastError();                          \
+            if (e != hipSuccess) return e;                                   \
+        }                                                                    \
+        return hipSuccess;                                                   \
     }
     MEC_SPECIALIZED_GEOS(X)
 #undef X
@@ -758,18 +774,27 @@ hipError_t mec_launch_gf_encode_spec(int d, int p, const GfEncArgs *args,
 hipError_t mec_launch_gf_matmul(const GfMatmulArgs *args, int n_dst, int n,
                                 hipStream_t stream) {
     if (args->bs_masks == nullptr) return hipErrorInvalidValue;
-    const dim3 grid = gf_grid(args->shard_len, kMatmulGridScale, n);
+    for (int b0 = 0; b0 < n; b0 += kMaxGridY) {
+        const int nb = n - b0 < kMaxGridY ? n - b0 : kMaxGridY;
+        GfMatmulArgs sl = *args;
+        sl.src += (int64_t)b0 * args->src_item_stride;
+        sl.dst += (int64_t)b0 * args->dst_item_stride;
+        const dim3 grid = gf_grid(args->shard_len, kMatmulGridScale, nb);
 #define CASE(E)                                                              \
     case E:                                                                  \
         hipLaunchKernelGGL((gf_matmul_bs_kernel<E>), grid, dim3(kWg), 0,     \
-                           stream, *args);                                   \
-        return hipGetLastError();
-    switch (n_dst) {
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-    default:
-        return hipErrorInvalidValue;
-    }
+                           stream, sl);                                      \
+        break;
+        switch (n_dst) {
+            CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+        default:
+            return hipErrorInvalidValue;
+        }
 #undef CASE
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t mec_launch_scatter_rows(const ScatterArgs *args,

@@ -186,6 +186,12 @@ def test_fused4_lengths_and_batches(tiles, n):
     encode_case(n, S, D * S, True)
 
 
+def test_fused4_second_round_of_workgroups():
+    """258 workgroups on 256 compute units, the last one holding a single
+    block: the kernel's second round, with a partial group in it."""
+    encode_case(4 * 256 + 5, T, D * T, True)
+
+
 @pytest.mark.parametrize("n", [3, 9])
 def test_fused4_row_stride_differs_from_shard_len(n):
     """A 1 MiB context called with a short block_len: rows lie 128 KiB
