@@ -320,8 +320,8 @@ mec_status mec_reconstruct_batch_mixed(mec_ctx *ctx, int n, uint8_t *shards,
  *     it is in scope (any row, or data rows only under data_only).
  *
  * n*(d+p) must fit in 32 bits (else MEC_ERR_INVALID_ARG); n is not limited
- * to 65535.  shard_len is one value for the whole call: per-item shard
- * lengths are out of scope.  The calls are synchronous, since the host
+ * to 65535.  shard_len is one value for the whole call; the _var calls
+ * below take a length per item.  The calls are synchronous, since the host
  * needs the verdicts to plan: one stream synchronise before planning, one
  * at the end, and no _async variant.  mec_decode_stream and
  * mec_heal_stream keep their own per-object host grouping.
@@ -336,6 +336,55 @@ mec_status mec_verify_reconstruct_batch_dev(
 mec_status mec_verify_reconstruct_batch(
     mec_ctx *ctx, int n, uint8_t *shards, uint8_t *sums,
     const uint8_t *read_mask, int64_t shard_len, int bitrot_algo,
+    int data_only, int rehash, uint8_t *present_out, uint8_t *item_status);
+
+/* ---- verified batch read, one shard length PER ITEM ---------------------
+ *
+ * The read-side twin of mec_encode_batch_var.  parallelReader.Read shortens
+ * shardSize for the last block of an object (cmd/erasure-decode.go:138-139)
+ * and an object of at most one block is only a short block, so every GET or
+ * heal batched across objects holds items of different shard lengths; since
+ * the shard size is ceil(len/d), rows of different lengths cannot be padded
+ * to a common one.  block_lens[i] (host, n entries, each in
+ * [1, block_size]) is item i's block length, as for mec_encode_batch_var;
+ * only S_i = ceil(len_i/d) matters here, so a caller that knows the shard
+ * length alone passes min(S_i*d, block_size), which gives the same S_i
+ * (INTEGRATION.md "Batching GETs of different sizes").
+ *
+ * Device layout, with S_i, stride_i, R_i as defined for
+ * mec_encode_batch_var (mec_var_row_offsets computes R_0..R_n for both
+ * directions) and total = d+p:
+ *   shards_dev: one buffer of total*R_n bytes; row s of item i at
+ *       total*R_i + s*stride_i, S_i bytes valid, rebuilt in place.  Bytes
+ *       [S_i, stride_i) never influence a result and are scratch after a
+ *       rebuild.  Rows not flagged in read_mask may hold anything and are
+ *       never hashed.
+ *   sums_dev: the fused layout, (i*total+s)*32, exactly what
+ *       mec_encode_batch_var_dev writes, so its digests feed straight back
+ *       in.
+ * read_mask, present_out, item_status, data_only, rehash and bitrot_algo
+ * are mec_verify_reconstruct_batch_dev's, unchanged: verified rows are
+ * never written; an item with fewer than d verified rows gets
+ * MEC_ERR_TOO_FEW_SHARDS in item_status and is left untouched while the
+ * rest proceeds; with item_status NULL such an item makes the call return
+ * MEC_ERR_TOO_FEW_SHARDS with nothing modified and present_out filled.
+ * Every argument error (n <= 0, a NULL buffer, a length outside
+ * [1, block_size], the algorithm, n*(d+p) past 32 bits) is reported before
+ * anything is launched or written.  n is not limited to 65535.  Any (d,p)
+ * works: the reconstruct kernels are generic, unlike the encode var call.
+ * Synchronous, two stream synchronises, no _async variant.
+ *
+ * The host-pointer variant takes rows packed at S_i (item i's total rows at
+ * total * sum_{j<i} S_j) and digests packed at 32 B, packs only the rows
+ * flagged in read_mask into pinned staging, uploads in one plain copy, and
+ * writes back only the rebuilt rows (and, with rehash, their digests). */
+mec_status mec_verify_reconstruct_batch_var_dev(
+    mec_ctx *ctx, int n, void *shards_dev, void *sums_dev,
+    const int64_t *block_lens, const uint8_t *read_mask, int bitrot_algo,
+    int data_only, int rehash, uint8_t *present_out, uint8_t *item_status);
+mec_status mec_verify_reconstruct_batch_var(
+    mec_ctx *ctx, int n, uint8_t *shards, uint8_t *sums,
+    const int64_t *block_lens, const uint8_t *read_mask, int bitrot_algo,
     int data_only, int rehash, uint8_t *present_out, uint8_t *item_status);
 
 /* ---- batch bitrot hash / verify ----------------------------------------

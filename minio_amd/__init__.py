@@ -33,6 +33,11 @@ surfaces 1:1 for tests and benchmarks:
                             (cmd/bitrot-streaming.go:161-200,
                              cmd/erasure-decode.go:127-235;
                              mec_verify_reconstruct_batch)
+  - Erasure.verify_reconstruct_batch_var
+                        <-> the same with a shard length per item: the last
+                            block of every object is short
+                            (cmd/erasure-decode.go:138-139;
+                             mec_verify_reconstruct_batch_var)
   - bitrot_verify       <-> bitrotVerify (cmd/bitrot.go:164-216)
 
 No CPU fallback exists: constructing an Erasure on a machine without a
@@ -127,6 +132,10 @@ def _load():
         vp, i32, vp, vp, u8p, i64, i32, i32, i32, u8p, u8p]
     lib.mec_verify_reconstruct_batch.argtypes = [
         vp, i32, u8p, u8p, u8p, i64, i32, i32, i32, u8p, u8p]
+    lib.mec_verify_reconstruct_batch_var_dev.argtypes = [
+        vp, i32, vp, vp, i64p, u8p, i32, i32, i32, u8p, u8p]
+    lib.mec_verify_reconstruct_batch_var.argtypes = [
+        vp, i32, u8p, u8p, i64p, u8p, i32, i32, i32, u8p, u8p]
     lib.mec_bitrot_sum_batch.argtypes =[vp, i32, i32, u8p, i64, i64, u8p]
     lib.mec_bitrot_sum_batch_dev.argtypes = [vp, i32, i32, vp, i64, i64, vp]
     lib.mec_bitrot_verify_batch.argtypes = [vp, i32, i32, u8p, i64, i64, u8p, u8p]
@@ -470,6 +479,76 @@ class Erasure:
                     if not pres[c]:
                         row[s] = raw[c * per:(c + 1) * per]
                         srow[s] = sraw[c * 32:(c + 1) * 32]
+            out.append(row)
+            if rehash:
+                sums_out.append(srow)
+        return out, sums_out, statuses, corrupt
+
+    def verify_reconstruct_batch_var(self, items, sums, data_only=False,
+                                     rehash=False,
+                                     algo: int = HIGHWAYHASH256S):
+        """verify_reconstruct_batch with a shard length PER ITEM
+        (mec_verify_reconstruct_batch_var): what a GET or heal batch across
+        objects holds, since parallelReader.Read shortens shardSize for the
+        last block of every object (cmd/erasure-decode.go:138-139).
+
+        Arguments and the return shape are verify_reconstruct_batch's; the
+        shards of one item share a length S_i, items may differ.  An item's
+        block length cannot be recovered from S_i alone and does not need
+        to be: the call is given len_i = S_i*d (capped at block_size), which
+        yields the same S_i = ceil(len_i/d) and so the same rows and
+        digests.  An item with
+        every row None comes back unchanged with status 3; it is passed to
+        the library with S_i = 1 and an all-zero mask."""
+        d, total = self.d, self.d + self.p
+        n = len(items)
+        if n == 0:
+            return [], ([] if rehash else None), [], []
+        assert len(sums) == n
+        sizes = []
+        for it, su in zip(items, sums):
+            assert len(it) == total and len(su) == total
+            lens = {len(s) for s in it if s is not None}
+            assert len(lens) <= 1, "the shards of an item share one length"
+            sizes.append(lens.pop() if lens else 1)
+            for s in range(total):
+                assert it[s] is None or (su[s] is not None
+                                         and len(su[s]) == 32), \
+                    "a row that was read needs its 32-byte digest"
+        read = bytes(0 if s is None else 1 for it in items for s in it)
+        nosum = b"\0" * 32
+        buf = ctypes.create_string_buffer(
+            b"".join(b"\0" * S if s is None else s
+                     for it, S in zip(items, sizes) for s in it),
+            total * sum(sizes))
+        sbuf = ctypes.create_string_buffer(
+            b"".join(nosum if h is None else h for su in sums for h in su),
+            n * total * 32)
+        if max(sizes) > self.shard_size():
+            raise MecError(6, "a shard is longer than ceil(block_size/d)")
+        # S*d may pass block_size by up to d-1 when d does not divide it
+        lens = (ctypes.c_int64 * n)(*[min(S * d, self.block_size)
+                                      for S in sizes])
+        present = ctypes.create_string_buffer(n * total)
+        status = ctypes.create_string_buffer(n)
+        _check(_lib.mec_verify_reconstruct_batch_var(
+            self._ck(), n, buf, sbuf, lens, read, algo,
+            1 if data_only else 0, 1 if rehash else 0, present, status))
+        statuses = list(status.raw)
+        pres, raw, sraw = present.raw, buf.raw, sbuf.raw
+        scope = d if data_only else total
+        out, sums_out, corrupt, off = [], ([] if rehash else None), [], 0
+        for i, (it, S) in enumerate(zip(items, sizes)):
+            corrupt.append([s for s in range(total)
+                            if read[i * total + s] and not pres[i * total + s]])
+            row, srow = list(it), list(sums[i])
+            if statuses[i] == MEC_OK:
+                for s in range(scope):
+                    c = i * total + s
+                    if not pres[c]:
+                        row[s] = raw[off + s * S:off + (s + 1) * S]
+                        srow[s] = sraw[c * 32:(c + 1) * 32]
+            off += total * S
             out.append(row)
             if rehash:
                 sums_out.append(srow)

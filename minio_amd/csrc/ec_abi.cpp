@@ -15,6 +15,7 @@
 #include "../../include/minio_ec.h"
 #include "gf_host.h"
 #include "kernels.h"
+#include "read_var_plan.h"
 #include "recon_plan.h"
 #include "var_plan.h"
 #include "verify_list.h"
@@ -141,6 +142,10 @@ struct mec_ctx {
     hipEvent_t ev_e[2] = {nullptr, nullptr};
     int e_idx = 0;
     mec::VarPlan vplan; /* reused across calls to keep its allocations */
+    /* per-item-length verified read: tile prefixes of the call's work
+     * lists, and the host offsets of the packed rows (host-pointer call) */
+    std::vector<int64_t> vtiles[MEC_KMAX_E + 1];
+    std::vector<int64_t> vhost_off;
 
     mec_status ensure(void **buf, size_t *cap, size_t need) {
         if (*cap >= need) return MEC_OK;
@@ -963,9 +968,14 @@ static mec_status mixed_plan_locked(mec_ctx *ctx, int n,
 
 /* Uploads ctx->plan and launches one kernel per output-row count in use.
  * Never synchronizes the stream; the only host wait is on the copy that
- * last read the pinned slot being refilled (two calls back). */
+ * last read the pinned slot being refilled (two calls back).
+ * With items_dev (the per-item-length read): the rows are in ctx->vplan's
+ * packed layout, items_dev is its item table on the device, shard_len is
+ * unused, and ctx->vtiles, the tile prefixes of the work lists, are staged
+ * behind them for gf_matmul_bs_mixed_var_kernel. */
 static mec_status mixed_launch_locked(mec_ctx *ctx, void *shards_dev,
-                                      int64_t shard_len) {
+                                      int64_t shard_len,
+                                      const int64_t *items_dev = nullptr) {
     const mec::ReconPlan &pl = ctx->plan;
     if (pl.entries.empty()) return MEC_OK;
     auto al16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
@@ -978,6 +988,13 @@ static mec_status mixed_launch_locked(mec_ctx *ctx, void *shards_dev,
         work_off[e] = end;
         end = al16(end + pl.work[e].size() * sizeof(mec::ReconWork));
     }
+    size_t tile_off[MEC_KMAX_E + 1] = {0};
+    if (items_dev)
+        for (int e = 1; e <= MEC_KMAX_E; e++) {
+            tile_off[e] = end;
+            if (!pl.work[e].empty())
+                end = al16(end + ctx->vtiles[e].size() * sizeof(int64_t));
+        }
 
     const int slot = ctx->x_idx & 1;
     ctx->x_idx ^= 1;
@@ -1006,11 +1023,34 @@ static mec_status mixed_launch_locked(mec_ctx *ctx, void *shards_dev,
         if (!pl.work[e].empty())
             memcpy(pinb + work_off[e], pl.work[e].data(),
                    pl.work[e].size() * sizeof(mec::ReconWork));
+    if (items_dev)
+        for (int e = 1; e <= MEC_KMAX_E; e++)
+            if (!pl.work[e].empty())
+                memcpy(pinb + tile_off[e], ctx->vtiles[e].data(),
+                       ctx->vtiles[e].size() * sizeof(int64_t));
     HIP_TRY(hipMemcpyAsync(ctx->dev_x, pinb, end, hipMemcpyHostToDevice,
                            ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev_x[slot], ctx->stream));
 
     const uint8_t *dx = (const uint8_t *)ctx->dev_x;
+    if (items_dev) {
+        GfMixedVarArgs v{};
+        v.shards = (uint8_t *)shards_dev;
+        v.items = items_dev;
+        v.entries = (const uint32_t *)dx;
+        v.masks = (const uint32_t *)(dx + mask_off);
+        v.d = ctx->d;
+        v.total = ctx->d + ctx->p;
+        for (int e = 1; e <= MEC_KMAX_E; e++) {
+            if (pl.work[e].empty()) continue;
+            v.work = (const uint32_t *)(dx + work_off[e]);
+            v.tiles = (const int64_t *)(dx + tile_off[e]);
+            v.n_work = (uint32_t)pl.work[e].size();
+            v.tiles_total = ctx->vtiles[e].back();
+            HIP_TRY(mec_launch_gf_matmul_mixed_var(&v, e, ctx->stream));
+        }
+        return MEC_OK;
+    }
     GfMixedArgs a{};
     a.shards = (uint8_t *)shards_dev;
     a.item_stride = (int64_t)(ctx->d + ctx->p) * ctx->stride;
@@ -1286,6 +1326,218 @@ mec_status mec_verify_reconstruct_batch(
     for (uint32_t c : ctx->vlist) {
         memcpy(shards + (size_t)c * shard_len, pinb + (size_t)c * stride,
                (size_t)shard_len);
+        if (rehash)
+            memcpy(sums + (size_t)c * 32, pinb + row_bytes + (size_t)c * 32,
+                   32);
+    }
+    return MEC_OK;
+}
+
+/* ---- verified batch read, one shard length PER ITEM --------------------- */
+
+/* parallelReader.Read shortens shardSize for the last block of an object
+ * (cmd/erasure-decode.go:138-139), so a GET or heal batch across objects
+ * has a shard length per item.  Everything that can be refused is refused
+ * here, before anything is launched or written; on MEC_OK ctx->vplan holds
+ * the call's item table and hash order. */
+static mec_status read_var_check_locked(mec_ctx *ctx, int n,
+                                        const void *shards, const void *sums,
+                                        const int64_t *block_lens,
+                                        const uint8_t *read_mask,
+                                        int bitrot_algo) {
+    if (n <= 0 || !shards || !sums || !block_lens || !read_mask)
+        return MEC_ERR_INVALID_ARG;
+    if (bitrot_algo != MEC_BITROT_HIGHWAYHASH256S &&
+        bitrot_algo != MEC_BITROT_HIGHWAYHASH256)
+        return MEC_ERR_INVALID_ARG;
+    /* also refuses n*(d+p) past 32 bits (chain ids) */
+    if (!mec::build_var_plan(ctx->d, ctx->d + ctx->p, ctx->block_size, n,
+                             block_lens, &ctx->vplan))
+        return MEC_ERR_INVALID_ARG;
+    return MEC_OK;
+}
+
+/* verify_recon_locked with ctx->vplan's packed rows: the lists are in the
+ * plan's hash order, the item table travels with the first list, and the
+ * mixed launch takes the tile prefixes along.  Same synchronisation: one
+ * before planning, the caller does the final one. */
+static mec_status verify_recon_var_locked(mec_ctx *ctx, int n,
+                                          void *shards_dev, void *sums_dev,
+                                          const uint8_t *read_mask,
+                                          int data_only, int rehash,
+                                          bool want_rebuilt,
+                                          uint8_t *present_out,
+                                          uint8_t *item_status) {
+    const int d = ctx->d, p = ctx->p, total = d + p;
+    const mec::VarPlan &vp = ctx->vplan;
+    uint32_t count;
+    if (!mec::verify_chain_count(n, total, &count)) return MEC_ERR_INVALID_ARG;
+    mec::build_verify_list_ordered(vp, total, read_mask, &ctx->vlist);
+    const size_t n_list = ctx->vlist.size();
+
+    /* [list, room for every chain | ok bytes | item table] */
+    auto al16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t ok_off = al16((size_t)count * sizeof(uint32_t));
+    const size_t item_off = al16(ok_off + count);
+    const size_t item_bytes = (size_t)n * sizeof(mec::VarItem);
+    const size_t need = item_off + item_bytes;
+    mec_status st;
+    if ((st = ctx->ensure(&ctx->dev_v, &ctx->cap_v, need)) != MEC_OK)
+        return st;
+    if (ctx->cap_pin_v < need) {
+        if (ctx->pin_v) (void)hipHostFree(ctx->pin_v);
+        ctx->pin_v = nullptr;
+        ctx->cap_pin_v = 0;
+        HIP_TRY(hipHostMalloc(&ctx->pin_v, need));
+        ctx->cap_pin_v = need;
+    }
+    uint8_t *pinb = (uint8_t *)ctx->pin_v;
+    uint8_t *dv = (uint8_t *)ctx->dev_v;
+    const int64_t *items_dev = (const int64_t *)(dv + item_off);
+
+    HashListVarArgs h{};
+    h.shards = (const uint8_t *)shards_dev;
+    h.sums = (uint8_t *)sums_dev;
+    h.ok = dv + ok_off;
+    h.list = (const uint32_t *)dv;
+    h.items = items_dev;
+    h.total = (uint32_t)total;
+    memcpy(h.key, kMagicHHKey, 32);
+
+    memcpy(pinb + item_off, vp.items.data(), item_bytes);
+    HIP_TRY(hipMemcpyAsync(dv + item_off, pinb + item_off, item_bytes,
+                           hipMemcpyHostToDevice, ctx->stream));
+    if (n_list) {
+        memcpy(pinb, ctx->vlist.data(), n_list * sizeof(uint32_t));
+        HIP_TRY(hipMemcpyAsync(dv, pinb, n_list * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(hipMemsetAsync(dv + ok_off, 0, count, ctx->stream));
+    h.n_list = (uint32_t)n_list;
+    HIP_TRY(mec_launch_hash_list_var(&h, 1, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(pinb + ok_off, dv + ok_off, count,
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+
+    ctx->vpresent.resize(count);
+    mec::merge_verified(count, read_mask, pinb + ok_off,
+                        ctx->vpresent.data());
+    if (present_out) memcpy(present_out, ctx->vpresent.data(), count);
+
+    st = mixed_plan_locked(ctx, n, ctx->vpresent.data(), data_only,
+                           item_status);
+    if (st != MEC_OK) return st;
+    for (int e = 1; e <= MEC_KMAX_E; e++)
+        if (!ctx->plan.work[e].empty() &&
+            !mec::build_tile_prefix(vp, ctx->plan.work[e], &ctx->vtiles[e]))
+            return MEC_ERR_INTERNAL;
+    if ((st = mixed_launch_locked(ctx, shards_dev, 0, items_dev)) != MEC_OK)
+        return st;
+
+    ctx->vlist.clear();
+    if ((rehash || want_rebuilt) && !ctx->plan.entries.empty())
+        mec::build_rehash_list_ordered(vp, ctx->plan, d, p,
+                                       ctx->vpresent.data(), data_only,
+                                       &ctx->vlist);
+    if (rehash && !ctx->vlist.empty()) {
+        /* the verify kernel and the list upload are done (synchronised
+         * above), so both list buffers can be refilled */
+        const size_t nb = ctx->vlist.size() * sizeof(uint32_t);
+        memcpy(pinb, ctx->vlist.data(), nb);
+        HIP_TRY(hipMemcpyAsync(dv, pinb, nb, hipMemcpyHostToDevice,
+                               ctx->stream));
+        h.n_list = (uint32_t)ctx->vlist.size();
+        HIP_TRY(mec_launch_hash_list_var(&h, 0, ctx->stream));
+    }
+    return MEC_OK;
+}
+
+mec_status mec_verify_reconstruct_batch_var_dev(
+    mec_ctx *ctx, int n, void *shards_dev, void *sums_dev,
+    const int64_t *block_lens, const uint8_t *read_mask, int bitrot_algo,
+    int data_only, int rehash, uint8_t *present_out, uint8_t *item_status) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mec_status st = read_var_check_locked(ctx, n, shards_dev, sums_dev,
+                                          block_lens, read_mask, bitrot_algo);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipSetDevice(ctx->device));
+    st = verify_recon_var_locked(ctx, n, shards_dev, sums_dev, read_mask,
+                                 data_only, rehash, false, present_out,
+                                 item_status);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MEC_OK;
+}
+
+mec_status mec_verify_reconstruct_batch_var(
+    mec_ctx *ctx, int n, uint8_t *shards, uint8_t *sums,
+    const int64_t *block_lens, const uint8_t *read_mask, int bitrot_algo,
+    int data_only, int rehash, uint8_t *present_out, uint8_t *item_status) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mec_status st = read_var_check_locked(ctx, n, shards, sums, block_lens,
+                                          read_mask, bitrot_algo);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const mec::VarPlan &vp = ctx->vplan;
+    const int total = ctx->d + ctx->p;
+    const uint32_t count = (uint32_t)((int64_t)n * total);
+    /* rows, then digests, in one device buffer: one upload */
+    const size_t row_bytes = (size_t)total * vp.rows_total;
+    const size_t sum_bytes = (size_t)count * 32;
+    if ((st = ctx->ensure(&ctx->dev_a, &ctx->cap_a, row_bytes + sum_bytes)) !=
+        MEC_OK)
+        return st;
+    if ((st = ctx->ensure_pin(row_bytes + sum_bytes)) != MEC_OK) return st;
+    uint8_t *pinb = (uint8_t *)ctx->pin;
+    uint8_t *dev_rows = (uint8_t *)ctx->dev_a;
+    uint8_t *dev_sums = dev_rows + row_bytes;
+    /* the caller's rows are packed at S_i: item i's rows start at
+     * total * sum_{j<i} S_j */
+    std::vector<int64_t> &hoff = ctx->vhost_off;
+    hoff.resize((size_t)n);
+    int64_t acc = 0;
+    for (int i = 0; i < n; i++) {
+        hoff[(size_t)i] = acc;
+        acc += vp.items[(size_t)i].shard_len;
+    }
+    /* only rows that were read are packed; the others' device bytes are
+     * whatever the buffer held, which nothing reads */
+    for (int i = 0; i < n; i++) {
+        const int64_t S = vp.items[(size_t)i].shard_len;
+        const int64_t stride = (S + 63) & ~int64_t(63);
+        const uint8_t *src = shards + (size_t)total * hoff[(size_t)i];
+        uint8_t *dst = pinb + (size_t)total * vp.items[(size_t)i].row_off;
+        for (int s = 0; s < total; s++)
+            if (read_mask[(size_t)i * total + s])
+                memcpy(dst + (size_t)s * stride, src + (size_t)s * S,
+                       (size_t)S);
+    }
+    memcpy(pinb + row_bytes, sums, sum_bytes);
+    HIP_TRY(hipMemcpyAsync(dev_rows, pinb, row_bytes + sum_bytes,
+                           hipMemcpyHostToDevice, ctx->stream));
+    st = verify_recon_var_locked(ctx, n, dev_rows, dev_sums, read_mask,
+                                 data_only, rehash, true, present_out,
+                                 item_status);
+    if (st != MEC_OK) return st;
+    if (ctx->vlist.empty()) { /* nothing was rebuilt */
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return MEC_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(pinb, dev_rows,
+                           row_bytes + (rehash ? sum_bytes : 0),
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    /* only rebuilt rows go back, with their fresh digests under rehash */
+    for (uint32_t c : ctx->vlist) {
+        const uint32_t i = c / (uint32_t)total, s = c - i * (uint32_t)total;
+        const int64_t S = vp.items[i].shard_len;
+        const int64_t stride = (S + 63) & ~int64_t(63);
+        memcpy(shards + (size_t)total * hoff[i] + (size_t)s * S,
+               pinb + (size_t)total * vp.items[i].row_off +
+                   (size_t)s * stride,
+               (size_t)S);
         if (rehash)
             memcpy(sums + (size_t)c * 32, pinb + row_bytes + (size_t)c * 32,
                    32);

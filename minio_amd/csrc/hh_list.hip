@@ -15,6 +15,7 @@
  *  - verify mode compares each lane's 8-byte output word with the expected
  *    digest, ANDs the four verdicts across the quad and stores one byte at
  *    ok[id]; no digest is written.  Sum mode stores the digest words.
+ *    (hh_quad.h's hh1_emit, shared with read_var.hip.)
  * msg_len is uniform per launch, so waves never diverge in the packet
  * loops; a list length that is no multiple of 16 leaves whole quads
  * inactive, never part of one, which is what hh_quad.h's quad contract asks.
@@ -41,16 +42,7 @@ __device__ __forceinline__ void hh256_list_body(const HashListArgs &a) {
     HH1_STREAM(s, mp, len, S3)
     if (RAGGED && len > 0) hh1_remainder(s, mp, (int)len, j, S3);
     const uint64_t out = hh1_finish(s, j, S3);
-    uint8_t *slot_p = a.sums + id * 32 + 8 * j;
-    if (VERIFY) {
-        const uint64_t want = *(const uint64_t *)slot_p;
-        uint32_t good = (out == want) ? 1u : 0u;
-        good &= dpp_swap1(good); /* pair verdict */
-        good &= dpp_swap2(good); /* quad verdict */
-        if (j == 0) a.ok[id] = (uint8_t)good;
-    } else {
-        *(uint64_t *)slot_p = out;
-    }
+    hh1_emit<VERIFY>(out, a.sums + id * 32 + 8 * j, a.ok + id, j);
 }
 
 /* two names, so a kernel trace tells the modes apart */

@@ -2,7 +2,8 @@
  * (lane selector, init, packet update, streaming loop, UpdateRemainder,
  * finish).  Every HighwayHash kernel of the library is built from it:
  * hh256_batch4_kernel (kernels.hip), hh256_list_* (hh_list.hip),
- * hh256_var_kernel (encode_var.hip) and the hash waves of
+ * hh256_var_kernel (encode_var.hip), hh256_list_var_* (read_var.hip) and
+ * the hash waves of
  * fused4_encode_hh_kernel (fused4.hip), which brings its own packet loop.
  * Device code only; why 4 lanes per chain: see the comment above
  * hh256_batch4_kernel in kernels.hip.
@@ -240,6 +241,26 @@ __device__ __forceinline__ uint64_t hh1_finish(HH1 &s, int j, uint32_t S3) {
     if ((j & 1) == 0) return t ^ (sv << 1) ^ (sv << 2);
     uint64_t a3 = sv & 0x3fffffffffffffffull;
     return t ^ ((a3 << 1) | (se >> 63)) ^ ((a3 << 2) | (se >> 62));
+}
+
+/* What the list-driven kernels (hh_list.hip, read_var.hip) do with digest
+ * word `out` of lane j, slot_p being that word's place in the chain's
+ * digest slot.  VERIFY: compare with the expected word, AND the four
+ * verdicts across the quad and store one byte at *ok_p; no digest is
+ * written.  Otherwise store the word.  The quad contract covers it: all
+ * four lanes of the chain call it together. */
+template <bool VERIFY>
+__device__ __forceinline__ void hh1_emit(uint64_t out, uint8_t *slot_p,
+                                         uint8_t *ok_p, int j) {
+    if (VERIFY) {
+        const uint64_t want = *(const uint64_t *)slot_p;
+        uint32_t good = (out == want) ? 1u : 0u;
+        good &= dpp_swap1(good); /* pair verdict */
+        good &= dpp_swap2(good); /* quad verdict */
+        if (j == 0) *ok_p = (uint8_t)good;
+    } else {
+        *(uint64_t *)slot_p = out;
+    }
 }
 
 #endif

@@ -82,6 +82,33 @@ struct HashListArgs {
     uint64_t key[4];
 };
 
+/* Verified read with a shard length per item (read_var.hip).  The packed
+ * layout is var_plan.h's with all d+p rows of an item together: row s of
+ * item i at shards + total*R_i + s*align64(S_i).  Tables: read_var_plan.h. */
+struct GfMixedVarArgs {
+    uint8_t *shards;         /* total*R_n bytes, rebuilt in place */
+    const int64_t *items;    /* 2 per item: R_i, S_i (mec::VarItem) */
+    const uint32_t *entries; /* plan table, 12 dwords per entry */
+    const uint32_t *masks;   /* packed bit matrices, all entries */
+    const uint32_t *work;    /* this launch's list: (item, entry) pairs */
+    const int64_t *tiles;    /* n_work+1: tile prefix T_0..T_m of the list */
+    int64_t tiles_total;     /* T_m */
+    uint32_t n_work;         /* pairs in the list */
+    int d;                   /* number of source rows */
+    int total;               /* d+p */
+};
+
+struct HashListVarArgs {
+    const uint8_t *shards;
+    uint8_t *sums;        /* verify: read only; sum: written */
+    uint8_t *ok;          /* verify only: one byte per chain ID */
+    const uint32_t *list; /* n_list chain ids, item*total+row */
+    const int64_t *items; /* 2 per item: R_i, S_i */
+    uint32_t n_list;
+    uint32_t total;       /* d+p */
+    uint64_t key[4];
+};
+
 /* Specialized-encode args (constexpr-matrix kernels) */
 struct GfEncArgs {
     const uint8_t *data;
@@ -170,6 +197,14 @@ hipError_t mec_launch_hash(int algo, const HashArgs *args, hipStream_t stream);
  * else hh256_list_sum.  n_list == 0 launches nothing. */
 hipError_t mec_launch_hash_list(const HashListArgs *args, int verify,
                                 hipStream_t stream);
+/* gf_matmul_bs_mixed_var_kernel<n_dst> over args->tiles_total tiles;
+ * n_work == 0 launches nothing */
+hipError_t mec_launch_gf_matmul_mixed_var(const GfMixedVarArgs *args,
+                                          int n_dst, hipStream_t stream);
+/* hh256_list_var_verify (verify != 0) or hh256_list_var_sum over
+ * args->list; n_list == 0 launches nothing */
+hipError_t mec_launch_hash_list_var(const HashListVarArgs *args, int verify,
+                                    hipStream_t stream);
 }
 
 #endif
