@@ -10,9 +10,10 @@
  *    an LDS ring with global_load_lds_dwordx4 (no VGPR, no ds_write: the
  *    ds_write_b128 issue cost is what sank the earlier LDS-ring attempts),
  *    one T-byte tile of every row per step, LA tiles ahead;
- *  - NGF GF waves read 32-B columns from that ring, run the bit-sliced
- *    transpose / fold / transpose of gf_bs.h, and write parity twice: to
- *    global memory (nontemporal) and into a small LDS parity ring;
+ *  - NGF GF waves read two 16-B half-columns per row from that ring, run
+ *    the bit-sliced transpose / fold / transpose of gf_bs.h (its
+ *    4-operation form, bs_transpose4), and write parity twice: to global
+ *    memory (nontemporal) and into a small LDS parity ring;
  *  - NHW hash waves (4 lanes per chain, hh_quad.h) hash data rows AND
  *    parity rows out of LDS; data chains and parity chains run the same
  *    code, only the per-lane base and the lag differ.
@@ -44,6 +45,27 @@
  * would hit the same banks.  The image stays linear — it has to — but row
  * r is stored rotated by (r mod 16) packets: the rotation is applied to
  * the loader's per-lane SOURCE address and to every reader's offset.
+ *
+ * GF lane mapping: lane (g, o), g = lane / 16 the block, o = lane % 16,
+ * holds 32 bytes of each row of block g's tile (GF is byte-wise, any 32 will
+ * do): bytes [16o, 16o+16) and [T/2 + 16o, T/2 + 16o + 16).  The rotation is
+ * a multiple of 32 B, so both pieces stay 16-B aligned and whole.  What the
+ * split buys over one 32-B column per lane:
+ *  - a global parity store instruction writes 256 contiguous bytes per
+ *    block, two whole 128-B lines, and every line is written once (a 32-B
+ *    lane stride wrote 16 B and skipped 16: half of every line, twice);
+ *  - a ds_read_b128 is served in four groups of 16 lanes over a 256-B bank
+ *    row.  Each group holds 8 lanes of block g and 8 of block g+1, whose
+ *    rows g*D+k and (g+1)*D+k are rotated by 32k and 32k + 256 ≡ 32k mod
+ *    256; their o values together are 0..15, so the group's addresses are
+ *    16 distinct 16-B slots of the bank row: conflict-free for g = 0..3,
+ *    k = 0..7, both halves (T/2 ≡ 0 mod 256).  The 32-B stride used only
+ *    the even slots, 2-way;
+ *  - a ds_write_b128 is served in groups of 8 contiguous lanes over a 128-B
+ *    bank row; 8 lanes x 16 B are 128 contiguous bytes (they were 256).
+ * Requesting all rows of a GF step ahead of the first fold (counted
+ * lgkmcnt) was built and measured neutral, so each row is read where it is
+ * used.
  *
  * Eligibility: a compiled specialisation, shard_len % T == 0; anything
  * else is hipErrorNotSupported and the caller takes the kernel pair.
@@ -177,13 +199,19 @@ fused4_encode_hh_kernel(FusedArgs a) {
 
     if (wid <= NGF) {
         /* ---- GF wave w owns tiles w, w+NGF, ...; lane = (block g,
-         * 32-B column o) ---- */
+         * half-column pair o): bytes [16o, 16o+16) and [T/2 + 16o,
+         * T/2 + 16o + 16) of each row of the tile ---- */
+        static_assert((T / 2) % (16 * (T / 32)) == 0,
+                      "the lanes of a block cover each half of a tile row "
+                      "in 16-B pieces");
         const int w = wid - 1;
         const int g = lane / (T / 32);
         const int o = lane % (T / 32);
+        const int xlo = o * 16, xhi = T / 2 + o * 16;
         const bool gact = g < G && b0 + g < a.n;
         const int gg = g < G ? g : 0; /* lanes past G mirror block 0 */
-        uint8_t *prow = a.parity + ((b0 + gg) * P) * stride + (int64_t)o * 32;
+        uint8_t *prow = a.parity + ((b0 + gg) * P) * stride + xlo;
+        typedef unsigned int v4u __attribute__((ext_vector_type(4)));
         uint32_t accp[P][8];
         step_barrier(); /* prologue */
         int64_t s = 0;
@@ -206,34 +234,35 @@ fused4_encode_hh_kernel(FusedArgs a) {
                     for (int k = 0; k < D; k++) {
                         if (k >= row_begin(D, NGF, ph) &&
                             k < row_begin(D, NGF, ph + 1)) {
-                            const uint8_t *q =
-                                dslot + rot_off(gg * D + k, o * 32);
-                            uint4 lo = *(const uint4 *)q;
-                            uint4 hi = *(const uint4 *)(q + 16);
+                            uint4 lo = *(const uint4 *)(
+                                dslot + rot_off(gg * D + k, xlo));
+                            uint4 hi = *(const uint4 *)(
+                                dslot + rot_off(gg * D + k, xhi));
                             uint32_t xc[8] = {lo.x, lo.y, lo.z, lo.w,
                                               hi.x, hi.y, hi.z, hi.w};
-                            bs_transpose(xc);
+                            bs_transpose4(xc);
                             bs_acc_k<D, P, MAT>(k, xc, accp);
                         }
                     }
                     if (ph == NGF - 1) {
 #pragma unroll
                         for (int i = 0; i < P; i++) {
-                            bs_transpose(accp[i]);
-                            typedef unsigned int v4u
-                                __attribute__((ext_vector_type(4)));
+                            bs_transpose4(accp[i]);
                             v4u vlo = {accp[i][0], accp[i][1], accp[i][2],
                                        accp[i][3]};
                             v4u vhi = {accp[i][4], accp[i][5], accp[i][6],
                                        accp[i][7]};
-                            uint8_t *lp = pslot + rot_off(gg * P + i, o * 32);
-                            *(v4u *)lp = vlo;
-                            *(v4u *)(lp + 16) = vhi;
-                            if (gact) {
+                            if (!(a.probe & 16)) {
+                                *(v4u *)(pslot + rot_off(gg * P + i, xlo)) =
+                                    vlo;
+                                *(v4u *)(pslot + rot_off(gg * P + i, xhi)) =
+                                    vhi;
+                            }
+                            if (gact && !(a.probe & 8)) {
                                 uint8_t *orow = prow + i * stride + t * T;
                                 __builtin_nontemporal_store(vlo, (v4u *)orow);
                                 __builtin_nontemporal_store(
-                                    vhi, (v4u *)(orow + 16));
+                                    vhi, (v4u *)(orow + T / 2));
                             }
                         }
                     }
@@ -310,8 +339,10 @@ extern "C" hipError_t mec_launch_fused4_encode_hh(int d, int p,
     if (!enabled) return hipErrorNotSupported;
     /* MEC_F4_LA: loader lookahead in tiles (2 or 3).  MEC_F4_PROBE: perf
      * isolation, results INVALID: bit 0 hash waves idle, bit 1 GF waves
-     * idle, bit 2 loader issues nothing.  Every wave still executes every
-     * barrier under any probe. */
+     * idle, bit 2 loader issues nothing, bit 3 GF waves skip the global
+     * parity stores (the LDS parity writes still run), bit 4 GF waves skip
+     * the LDS parity writes (the parity chains hash stale bytes).  Every
+     * wave still executes every barrier under any combination of bits. */
     static const int f4la = [] {
         const char *v = getenv("MEC_F4_LA");
         return v ? atoi(v) : 2;

@@ -47,6 +47,112 @@ __device__ __forceinline__ void bs_transpose(uint32_t r[8]) {
     bs_pair(r[3], r[7], 4, 0xF0F0F0F0u);
 }
 
+/* ---- the same transpose in 4 VALU per exchange --------------------------
+ *
+ * A delta-swap is shift, bitop3, xor, shift, xor.  The exchange it performs
+ * is also two bit-field selects, each one v_bitop3 on a shifted operand:
+ *   A' = (A & ~m) | ((B << s) & m)      B' = (B & m) | ((A >> s) & ~m)
+ * (m >> s == ~m for the three stage masks): 48 operations per transpose
+ * instead of 60.  The network is written once over an operation policy, so
+ * that the device code and the compile-time proof below run the same stages
+ * with the same truth tables. */
+constexpr uint8_t BS_SEL_C_BA = 0xD8; /* bitop3(a, b, c): c ? b : a */
+constexpr uint8_t BS_SEL_C_AB = 0xE4; /* bitop3(a, b, c): c ? a : b */
+
+template <class Op>
+__host__ __device__ constexpr void bs_pair4_net(uint32_t &A, uint32_t &B,
+                                                int s, uint32_t m) {
+    const uint32_t a = Op::bitop3(A, B << s, m, BS_SEL_C_BA);
+    B = Op::bitop3(B, A >> s, m, BS_SEL_C_AB);
+    A = a;
+}
+
+template <class Op>
+__host__ __device__ constexpr void bs_transpose4_net(uint32_t r[8]) {
+    bs_pair4_net<Op>(r[0], r[1], 1, 0xAAAAAAAAu);
+    bs_pair4_net<Op>(r[2], r[3], 1, 0xAAAAAAAAu);
+    bs_pair4_net<Op>(r[4], r[5], 1, 0xAAAAAAAAu);
+    bs_pair4_net<Op>(r[6], r[7], 1, 0xAAAAAAAAu);
+    bs_pair4_net<Op>(r[0], r[2], 2, 0xCCCCCCCCu);
+    bs_pair4_net<Op>(r[1], r[3], 2, 0xCCCCCCCCu);
+    bs_pair4_net<Op>(r[4], r[6], 2, 0xCCCCCCCCu);
+    bs_pair4_net<Op>(r[5], r[7], 2, 0xCCCCCCCCu);
+    bs_pair4_net<Op>(r[0], r[4], 4, 0xF0F0F0F0u);
+    bs_pair4_net<Op>(r[1], r[5], 4, 0xF0F0F0F0u);
+    bs_pair4_net<Op>(r[2], r[6], 4, 0xF0F0F0F0u);
+    bs_pair4_net<Op>(r[3], r[7], 4, 0xF0F0F0F0u);
+}
+
+struct BsOpDevice {
+    static __device__ __forceinline__ uint32_t bitop3(uint32_t a, uint32_t b,
+                                                      uint32_t c,
+                                                      uint8_t tbl) {
+        /* the table must be an immediate */
+        return tbl == BS_SEL_C_BA
+                   ? (uint32_t)__builtin_amdgcn_bitop3_b32(a, b, c,
+                                                           BS_SEL_C_BA)
+                   : (uint32_t)__builtin_amdgcn_bitop3_b32(a, b, c,
+                                                           BS_SEL_C_AB);
+    }
+};
+
+/* v_bitop3_b32 as the ISA defines it: result bit = tbl[a*4 + b*2 + c] */
+struct BsOpModel {
+    static constexpr uint32_t bitop3(uint32_t a, uint32_t b, uint32_t c,
+                                     uint8_t tbl) {
+        uint32_t r = 0;
+        for (int idx = 0; idx < 8; idx++)
+            if ((tbl >> idx) & 1)
+                r |= ((idx & 4) ? a : ~a) & ((idx & 2) ? b : ~b) &
+                     ((idx & 1) ? c : ~c);
+        return r;
+    }
+};
+
+/* bs_transpose's delta-swap network in plain C++, for the proof only */
+constexpr void bs_transpose_model(uint32_t r[8]) {
+    constexpr int ia[12] = {0, 2, 4, 6, 0, 1, 4, 5, 0, 1, 2, 3};
+    constexpr int ib[12] = {1, 3, 5, 7, 2, 3, 6, 7, 4, 5, 6, 7};
+    constexpr int sh[3] = {1, 2, 4};
+    constexpr uint32_t mk[3] = {0xAAAAAAAAu, 0xCCCCCCCCu, 0xF0F0F0F0u};
+    for (int e = 0; e < 12; e++) {
+        const int s = sh[e / 4];
+        const uint32_t t = ((r[ib[e]] << s) ^ r[ia[e]]) & mk[e / 4];
+        r[ia[e]] ^= t;
+        r[ib[e]] ^= t >> s;
+    }
+}
+
+/* Both networks are linear over GF(2), so equality on the 256 single-bit
+ * states (and on zero) is equality on every input; a few dense states ride
+ * along.  Evaluated by every build, host and device pass. */
+constexpr bool bs_transpose4_equals_delta_swap() {
+    for (int n = 0; n < 256 + 8; n++) {
+        uint32_t x[8] = {}, y[8] = {};
+        if (n < 256) {
+            x[n / 32] = 1u << (n % 32);
+        } else {
+            uint32_t v = 0x9E3779B9u * (uint32_t)(n - 255);
+            for (int i = 0; i < 8; i++) {
+                v ^= v << 13; v ^= v >> 17; v ^= v << 5;
+                x[i] = v;
+            }
+        }
+        for (int i = 0; i < 8; i++) y[i] = x[i];
+        bs_transpose_model(x);
+        bs_transpose4_net<BsOpModel>(y);
+        for (int i = 0; i < 8; i++)
+            if (x[i] != y[i]) return false;
+    }
+    return true;
+}
+static_assert(bs_transpose4_equals_delta_swap(),
+              "the 4-operation transpose must equal bs_transpose");
+
+__device__ __forceinline__ void bs_transpose4(uint32_t r[8]) {
+    bs_transpose4_net<BsOpDevice>(r);
+}
+
 /* constexpr GF(2^8)/0x11D multiply and bit-matrix row masks */
 constexpr uint8_t bs_gfmul(uint8_t a, uint8_t b) {
     uint32_t r = 0, x = a;
