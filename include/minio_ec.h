@@ -410,6 +410,63 @@ mec_status mec_bitrot_verify_stream(mec_ctx *ctx, const uint8_t *stream,
                                     int algo, const uint8_t *want_sum,
                                     int64_t shard_size);
 
+/* ---- batch scrub: many on-disk shard files in one call -------------------
+ *
+ * xlStorage.VerifyFile -> bitrotVerify (cmd/xl-storage.go:3082-3137,
+ * cmd/bitrot.go:164-216) over n shard files in the on-disk [hash||shard]*
+ * format, each with its own size, part size and shard size: what the
+ * scanner's deep scan and healObject run over every part of every object on
+ * a drive.  The frames are hashed where they lie; nothing is re-packed.
+ *
+ *   files_dev   one device buffer of files_bytes bytes, never written.
+ *   file_off    host, n: byte offset of file f in files_dev, ANY alignment
+ *               (mec_scrub_file_offsets gives a convenient layout).
+ *   file_sizes  host, n: bytes actually present (bitrotVerify's wantSize).
+ *   part_sizes  host, n: erasure.ShardFileSize(part.Size), >= 0.
+ *   shard_sizes host, n: erasure.ShardSize(), >= 1.
+ *   bitrot_algo MEC_BITROT_HIGHWAYHASH256S only.
+ *   file_status host, n: MEC_OK or MEC_ERR_FILE_CORRUPT per file.
+ *   first_bad   host, n, may be NULL: the lowest failing frame index, the
+ *               frame the reference stops at; -1 for an intact file.
+ *
+ * Per file, as bitrotVerify: if file_sizes[f] !=
+ * mec_bitrot_shard_file_size(part_sizes[f], shard_sizes[f], HH256S) the file
+ * is MEC_ERR_FILE_CORRUPT with first_bad -1 and nothing of it is hashed.
+ * Otherwise it has ceil(part/shard) frames at pitch 32 + shard, each 32
+ * digest bytes followed by the message, the last message of
+ * part - (frames-1)*shard bytes; any mismatching frame makes the file
+ * MEC_ERR_FILE_CORRUPT.  part_size 0 is MEC_OK with nothing hashed.  Bytes
+ * outside a frame never influence its verdict.
+ *
+ * The call returns MEC_OK whatever the verdicts are: one corrupt file does
+ * not fail the batch.  Argument errors (n <= 0, a NULL required pointer, a
+ * negative size, shard_size < 1, file_off < 0,
+ * file_off + file_size > files_bytes, another algorithm, more than 2^32-1
+ * frames to hash) return MEC_ERR_INVALID_ARG before anything is launched and
+ * before file_status or first_bad is written.  Independent of the context's
+ * (d,p) and block size; n is not limited to 65535.  Synchronous, one stream
+ * synchronise, no _async variant.
+ *
+ * The host-pointer variant takes one pointer per file (it may be NULL for a
+ * file of size 0), packs the files at mec_scrub_file_offsets offsets into
+ * pinned staging, uploads them in one plain copy and runs the device path.
+ *
+ * mec_scrub_file_offsets: pure host math, no context, no GPU.  F_0 = 0,
+ * F_{f+1} = F_f + align64(file_sizes[f]); writes n+1 entries.
+ * MEC_ERR_INVALID_ARG for n <= 0, a NULL pointer or a negative size. */
+mec_status mec_scrub_file_offsets(int n, const int64_t *file_sizes,
+                                  int64_t *file_off);
+mec_status mec_bitrot_verify_files_dev(
+    mec_ctx *ctx, int n, const void *files_dev, int64_t files_bytes,
+    const int64_t *file_off, const int64_t *file_sizes,
+    const int64_t *part_sizes, const int64_t *shard_sizes, int bitrot_algo,
+    uint8_t *file_status, int64_t *first_bad);
+mec_status mec_bitrot_verify_files(
+    mec_ctx *ctx, int n, const uint8_t *const *files,
+    const int64_t *file_sizes, const int64_t *part_sizes,
+    const int64_t *shard_sizes, int bitrot_algo, uint8_t *file_status,
+    int64_t *first_bad);
+
 /* ---- streaming-format host mirrors (C++ host driver over the kernels) --
  *
  * mec_encode_stream: Erasure.Encode loop (cmd/erasure-encode.go:76-108)

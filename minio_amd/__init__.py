@@ -140,6 +140,11 @@ def _load():
     lib.mec_bitrot_sum_batch_dev.argtypes = [vp, i32, i32, vp, i64, i64, vp]
     lib.mec_bitrot_verify_batch.argtypes = [vp, i32, i32, u8p, i64, i64, u8p, u8p]
     lib.mec_bitrot_verify_stream.argtypes = [vp, u8p, i64, i64, i32, u8p, i64]
+    lib.mec_scrub_file_offsets.argtypes = [i32, i64p, i64p]
+    lib.mec_bitrot_verify_files_dev.argtypes = [
+        vp, i32, vp, i64, i64p, i64p, i64p, i64p, i32, u8p, i64p]
+    lib.mec_bitrot_verify_files.argtypes = [
+        vp, i32, c.POINTER(u8p), i64p, i64p, i64p, i32, u8p, i64p]
     lib.mec_encode_stream.argtypes = [vp, u8p, i64, i32, c.POINTER(u8p), u8p]
     lib.mec_decode_stream.argtypes = [vp, c.POINTER(u8p), u8p, i32, i64, i64, i64, u8p]
     lib.mec_heal_stream.argtypes = [vp, c.POINTER(u8p), i32, i64, c.POINTER(u8p)]
@@ -204,6 +209,17 @@ def var_row_offsets(d: int, block_size: int, lens) -> list:
     arr = (ctypes.c_int64 * max(n, 1))(*lens)
     out = (ctypes.c_int64 * (n + 1))()
     _check(_lib.mec_var_row_offsets(d, block_size, n, arr, out))
+    return list(out)
+
+
+def scrub_file_offsets(sizes) -> list:
+    """Offsets F_0..F_n of the batch scrub's convenience layout
+    (mec_scrub_file_offsets): F_{f+1} = F_f + align64(sizes[f]).  Raises
+    MecError(6) for an empty list or a negative size."""
+    n = len(sizes)
+    arr = (ctypes.c_int64 * max(n, 1))(*sizes)
+    out = (ctypes.c_int64 * (n + 1))()
+    _check(_lib.mec_scrub_file_offsets(n, arr, out))
     return list(out)
 
 
@@ -638,3 +654,22 @@ class Erasure:
             return True
         except FileCorruptError:
             return False
+
+    def bitrot_verify_files(self, files, part_sizes, shard_sizes):
+        """Batch scrub (mec_bitrot_verify_files): bitrotVerify for
+        HighwayHash256S over many on-disk [hash||shard]* shard files in one
+        call.  files[f] is the file's bytes as present on the drive,
+        part_sizes[f] its erasure.ShardFileSize(part.Size), shard_sizes[f]
+        its erasure.ShardSize().  Returns (status, first_bad): status[f] is
+        0 or 5 (file corrupt), first_bad[f] the lowest failing frame, -1
+        for an intact file and for a file of the wrong size."""
+        n = len(files)
+        i64n = ctypes.c_int64 * max(n, 1)
+        ptrs = (ctypes.c_char_p * max(n, 1))(*files)
+        sizes = i64n(*[len(f) for f in files])
+        status = ctypes.create_string_buffer(max(n, 1))
+        first_bad = i64n()
+        _check(_lib.mec_bitrot_verify_files(
+            self._ck(), n, ptrs, sizes, i64n(*part_sizes),
+            i64n(*shard_sizes), HIGHWAYHASH256S, status, first_bad))
+        return list(status.raw[:n]), list(first_bad)[:n]

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "read_var_plan.h"
 #include "recon_plan.h"
+#include "scrub_plan.h"
 #include "var_plan.h"
 #include "verify_list.h"
 
@@ -146,6 +147,12 @@ struct mec_ctx {
      * lists, and the host offsets of the packed rows (host-pointer call) */
     std::vector<int64_t> vtiles[MEC_KMAX_E + 1];
     std::vector<int64_t> vhost_off;
+
+    /* batch scrub: the plan of one call; its tables and ok bytes go through
+     * dev_v / pin_v, the host-pointer variant's files through dev_a / pin */
+    mec::ScrubPlan splan;
+    std::vector<int64_t> shost_off;
+    std::vector<uint8_t> scorrupt;
 
     mec_status ensure(void **buf, size_t *cap, size_t need) {
         if (*cap >= need) return MEC_OK;
@@ -1635,6 +1642,139 @@ mec_status mec_bitrot_verify_batch(mec_ctx *ctx, int algo, int n,
         ok_out[i] = memcmp(got.data() + (size_t)i * hsz,
                            want + (size_t)i * hsz, (size_t)hsz) == 0;
     return MEC_OK;
+}
+
+/* ---- batch scrub -------------------------------------------------------- */
+
+mec_status mec_scrub_file_offsets(int n, const int64_t *file_sizes,
+                                  int64_t *file_off) {
+    return mec::scrub_file_offsets(n, file_sizes, file_off)
+               ? MEC_OK
+               : MEC_ERR_INVALID_ARG;
+}
+
+/* Hash ctx->splan's chains over files_dev and reduce: the tables go up in
+ * one copy, at most two launches, the ok bytes come back in one copy, one
+ * stream synchronise. */
+static mec_status scrub_run_locked(mec_ctx *ctx, const void *files_dev,
+                                   uint8_t *file_status, int64_t *first_bad) {
+    const mec::ScrubPlan &pl = ctx->splan;
+    const size_t n = pl.files.size();
+    const size_t na = pl.aligned.size(), ns = pl.sheared.size();
+    const size_t count = na + ns;
+    const uint8_t *ok = nullptr;
+    if (count) {
+        /* [file table | aligned list | sheared list | ok bytes] */
+        auto al16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+        const size_t tab_bytes = n * sizeof(mec::ScrubFile);
+        const size_t list_off = al16(tab_bytes);
+        const size_t ok_off = al16(list_off + count * sizeof(mec::ScrubChain));
+        const size_t need = ok_off + count;
+        mec_status st;
+        if ((st = ctx->ensure(&ctx->dev_v, &ctx->cap_v, need)) != MEC_OK)
+            return st;
+        if (ctx->cap_pin_v < need) {
+            if (ctx->pin_v) (void)hipHostFree(ctx->pin_v);
+            ctx->pin_v = nullptr;
+            ctx->cap_pin_v = 0;
+            HIP_TRY(hipHostMalloc(&ctx->pin_v, need));
+            ctx->cap_pin_v = need;
+        }
+        uint8_t *pinb = (uint8_t *)ctx->pin_v;
+        uint8_t *dv = (uint8_t *)ctx->dev_v;
+        memcpy(pinb, pl.files.data(), tab_bytes);
+        if (na)
+            memcpy(pinb + list_off, pl.aligned.data(),
+                   na * sizeof(mec::ScrubChain));
+        if (ns)
+            memcpy(pinb + list_off + na * sizeof(mec::ScrubChain),
+                   pl.sheared.data(), ns * sizeof(mec::ScrubChain));
+        HIP_TRY(hipMemcpyAsync(dv, pinb, ok_off, hipMemcpyHostToDevice,
+                               ctx->stream));
+        HashFramesArgs h{};
+        h.files = (const uint8_t *)files_dev;
+        h.table = (const int64_t *)dv;
+        memcpy(h.key, kMagicHHKey, 32);
+        h.list = (const uint32_t *)(dv + list_off);
+        h.ok = dv + ok_off;
+        h.n_list = (uint32_t)na;
+        HIP_TRY(mec_launch_hash_frames(&h, 0, ctx->stream));
+        h.list += 2 * na;
+        h.ok += na;
+        h.n_list = (uint32_t)ns;
+        HIP_TRY(mec_launch_hash_frames(&h, 1, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(pinb + ok_off, dv + ok_off, count,
+                               hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        ok = pinb + ok_off;
+    }
+    ctx->scorrupt.resize(n);
+    mec::reduce_scrub(pl, ok, ctx->scorrupt.data(), first_bad);
+    for (size_t f = 0; f < n; f++)
+        file_status[f] =
+            ctx->scorrupt[f] ? (uint8_t)MEC_ERR_FILE_CORRUPT : (uint8_t)MEC_OK;
+    return MEC_OK;
+}
+
+mec_status mec_bitrot_verify_files_dev(
+    mec_ctx *ctx, int n, const void *files_dev, int64_t files_bytes,
+    const int64_t *file_off, const int64_t *file_sizes,
+    const int64_t *part_sizes, const int64_t *shard_sizes, int bitrot_algo,
+    uint8_t *file_status, int64_t *first_bad) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    if (n <= 0 || !files_dev || !file_status ||
+        bitrot_algo != MEC_BITROT_HIGHWAYHASH256S)
+        return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!mec::build_scrub_plan(n, file_off, file_sizes, part_sizes,
+                               shard_sizes, files_bytes,
+                               (unsigned)((uintptr_t)files_dev & 7),
+                               &ctx->splan))
+        return MEC_ERR_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return scrub_run_locked(ctx, files_dev, file_status, first_bad);
+}
+
+mec_status mec_bitrot_verify_files(mec_ctx *ctx, int n,
+                                   const uint8_t *const *files,
+                                   const int64_t *file_sizes,
+                                   const int64_t *part_sizes,
+                                   const int64_t *shard_sizes,
+                                   int bitrot_algo, uint8_t *file_status,
+                                   int64_t *first_bad) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    if (n <= 0 || !files || !file_sizes || !file_status ||
+        bitrot_algo != MEC_BITROT_HIGHWAYHASH256S)
+        return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    std::vector<int64_t> &off = ctx->shost_off;
+    off.resize((size_t)n + 1);
+    if (!mec::scrub_file_offsets(n, file_sizes, off.data()))
+        return MEC_ERR_INVALID_ARG;
+    for (int f = 0; f < n; f++)
+        if (file_sizes[f] > 0 && !files[f]) return MEC_ERR_INVALID_ARG;
+    /* the staging buffers are 64-byte aligned and so is every offset */
+    if (!mec::build_scrub_plan(n, off.data(), file_sizes, part_sizes,
+                               shard_sizes, off[(size_t)n], 0, &ctx->splan))
+        return MEC_ERR_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    /* nothing to hash: the verdicts are all early ones */
+    if (ctx->splan.aligned.empty() && ctx->splan.sheared.empty())
+        return scrub_run_locked(ctx, nullptr, file_status, first_bad);
+    const size_t bytes = (size_t)off[(size_t)n];
+    mec_status st;
+    if ((st = ctx->ensure(&ctx->dev_a, &ctx->cap_a, bytes)) != MEC_OK)
+        return st;
+    if ((st = ctx->ensure_pin(bytes)) != MEC_OK) return st;
+    uint8_t *pinb = (uint8_t *)ctx->pin;
+    /* a file with an early verdict is never read on the device: only the
+     * files that are hashed are packed */
+    for (int f = 0; f < n; f++)
+        if (ctx->splan.files[(size_t)f].frames)
+            memcpy(pinb + off[(size_t)f], files[f], (size_t)file_sizes[f]);
+    HIP_TRY(hipMemcpyAsync(ctx->dev_a, pinb, bytes, hipMemcpyHostToDevice,
+                           ctx->stream));
+    return scrub_run_locked(ctx, ctx->dev_a, file_status, first_bad);
 }
 
 /* ---- device memory + timing helpers ------------------------------------ */

@@ -109,6 +109,21 @@ struct HashListVarArgs {
     uint64_t key[4];
 };
 
+/* Batch scrub (hh_frames.hip): chains are frames of on-disk shard files,
+ * hashed where they lie.  Chain c = list[2c], list[2c+1] = (file, frame);
+ * file f's table row is 4 qwords (mec::ScrubFile: off, shard, last,
+ * frames).  The frame starts at files + off + frame*(32+shard): 32 digest
+ * bytes, then the message.  ok[c] = 1 where the digest matches.  Tables:
+ * scrub_plan.h. */
+struct HashFramesArgs {
+    const uint8_t *files; /* never written */
+    const int64_t *table; /* 4 qwords per file */
+    const uint32_t *list; /* 2 dwords per chain */
+    uint8_t *ok;          /* one byte per chain, in list order */
+    uint32_t n_list;
+    uint64_t key[4];
+};
+
 /* Specialized-encode args (constexpr-matrix kernels) */
 struct GfEncArgs {
     const uint8_t *data;
@@ -205,6 +220,11 @@ hipError_t mec_launch_gf_matmul_mixed_var(const GfMixedVarArgs *args,
  * args->list; n_list == 0 launches nothing */
 hipError_t mec_launch_hash_list_var(const HashListVarArgs *args, int verify,
                                     hipStream_t stream);
+/* hh256_frames_verify (sheared == 0: every message address of the list is a
+ * multiple of 8) or hh256_frames_verify_sheared (none is) over args->list;
+ * n_list == 0 launches nothing */
+hipError_t mec_launch_hash_frames(const HashFramesArgs *args, int sheared,
+                                  hipStream_t stream);
 }
 
 #endif
