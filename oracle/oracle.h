@@ -22,15 +22,27 @@
  *    fingerprints (cmd/erasure-coding.go:177).
  *
  * Parity status: erasure matrix + HH256/SHA256/BLAKE2b pinned bit-exactly by
- * the reference's own golden vectors (tests/golden/).  HighwayHash ragged
- * tails (len % 32 != 0) are pinned transitively: the golden vectors cover
- * only multiples of 32; ragged behaviour follows the published portable
- * reference and is cross-checked oracle-vs-HIP in tests.
- * r2 hardening (external ragged vectors remain unobtainable offline —
- * DESIGN.md §2): the GPU cross-check covers EVERY len%32 residue, and a
- * second independently-written AVX2 main loop (simd.c) agrees with this
- * restatement for lengths 0..63 (test_simd_matches_scalar); the two share
- * only the UpdateRemainder code, which stays single-sourced.
+ * the reference's own golden vectors (tests/golden/): the boot self-test
+ * vectors, which for HighwayHash reach only lengths that are multiples of
+ * 32, and tests/golden/reference_shards/, whole objects as a reference
+ * server wrote them to disk ([hash||shard] per row, geometry, MD5 etag;
+ * tools/extract_reference_shards.py).  Those files pin, by bytes this
+ * project did not compute (tests/test_oracle_golden.py on the CPU,
+ * tests/test_gpu_reference_shards.py for every HIP kernel family):
+ *  - HighwayHash ragged tails at len % 32 = 18, 21 and 24, i.e. the
+ *    `size_mod32 & 16` branch of UpdateRemainder with len % 4 = 2, 1, 0,
+ *    the length injection and the rotate at those lengths;
+ *  - the main loop at 66048 and 214840 bytes;
+ *  - Split's zero pad, the EC2+2 and EC3+2 matrices in encode and in every
+ *    reconstruct pattern, and placement by EcIndex/EcDist.
+ * Still single-sourced (this file and hh1_remainder in hh_quad.h follow the
+ * same reading of the published portable reference): the
+ * `else if (size_mod4)` branch, i.e. len % 32 in 1..15 with len % 4 != 0,
+ * and len % 4 == 3 in either branch.  Those are covered only by the GPU
+ * cross-check over EVERY len % 32 residue, the static_assert byte map in
+ * hh_quad.h, and a second independently-written AVX2 main loop (simd.c)
+ * that agrees with this restatement for lengths 0..63
+ * (test_simd_matches_scalar) but shares its UpdateRemainder code.
  */
 #ifndef MINIO_AMD_ORACLE_H
 #define MINIO_AMD_ORACLE_H
