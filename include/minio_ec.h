@@ -205,6 +205,67 @@ mec_status mec_encode_batch_var(mec_ctx *ctx, int n, const uint8_t *data,
                                 const int64_t *block_lens, uint8_t *parity,
                                 int bitrot_algo, uint8_t *sums);
 
+/* ---- batch encode into on-disk [hash||shard] frames, length PER ITEM -----
+ *
+ * mec_encode_batch_var* ends with parity rows at a 64-byte stride and the
+ * digests in a separate table.  A drive stores neither: it stores
+ * streamingBitrotWriter's [hash||shard]* stream
+ * (cmd/bitrot-streaming.go:44-75), the format mec_bitrot_verify_files*
+ * scrubs.  These calls take the same input as mec_encode_batch_var* and
+ * leave, per logical shard row, one contiguous byte stream that is exactly
+ * what goes to that row's drive, ready for one D2H or one send.
+ *
+ * Output layout: defined by the lengths alone.  With S_i = ceil(len_i/d) and
+ * total = d+p,
+ *   F_0 = 0, F_{i+1} = F_i + 32 + S_i        (mec_frame_offsets)
+ *   frames: total*F_n bytes; row s's stream is [s*F_n, (s+1)*F_n); in it
+ *           item i's frame at F_i: the 32-byte HighwayHash-256 digest (magic
+ *           key) of the S_i shard bytes, then those bytes.  Data rows hold
+ *           Split's zero-padded contents, parity rows the encode's.
+ * Every byte of frames is defined after the call: no stride, no scratch.
+ * Consecutive blocks of one object passed as consecutive items make
+ * [F_first, F_{last+1}) of row s that object's shard file for logical row s,
+ * byte for byte what mec_encode_stream writes; the shim applies Distribution
+ * as for every other call (INTEGRATION.md "Shard distribution").
+ *
+ * data_dev is mec_encode_batch_var_dev's packed data (d*R_n bytes, R from
+ * mec_var_row_offsets) and is never written.  frames_dev may have any byte
+ * alignment; exactly total*F_n bytes are written and nothing outside them.
+ * Parity, digests and tables live in the context's grow-only buffers.
+ * bitrot_algo is MEC_BITROT_HIGHWAYHASH256S or MEC_BITROT_HIGHWAYHASH256;
+ * the geometry needs a compiled (d,p) specialization as above.  Every
+ * argument error (n <= 0, a NULL pointer, a length outside [1, block_size],
+ * n*(d+p) past 32 bits, the algorithm, the geometry) returns
+ * MEC_ERR_INVALID_ARG before anything is launched or written.  n is not
+ * limited to 65535.  Three kernels per call whatever the lengths.
+ *
+ * mec_frame_offsets is pure host math: no context, no GPU.  It writes
+ * F_0..F_n into frame_off (n+1 entries) and returns MEC_ERR_INVALID_ARG,
+ * with nothing written, for n <= 0, a NULL pointer or a length outside
+ * [1, block_size].
+ * _async does not synchronize the stream (pair with mec_stream_sync);
+ * back-to-back _async calls with different length tables and different
+ * output buffers need no sync in between: the shared scratch is ordered by
+ * the stream.  The host-pointer variant takes data as the blocks
+ * concatenated, sum(len_i) bytes, does the Split scatter into pinned
+ * staging, one plain upload (no overlapped ingest), and one D2H of
+ * total*F_n bytes into frames. */
+mec_status mec_frame_offsets(int data_shards, int64_t block_size, int n,
+                             const int64_t *block_lens, int64_t *frame_off);
+mec_status mec_encode_frames_batch_var_dev(mec_ctx *ctx, int n,
+                                           const void *data_dev,
+                                           const int64_t *block_lens,
+                                           void *frames_dev, int bitrot_algo);
+mec_status mec_encode_frames_batch_var_dev_async(mec_ctx *ctx, int n,
+                                                 const void *data_dev,
+                                                 const int64_t *block_lens,
+                                                 void *frames_dev,
+                                                 int bitrot_algo);
+mec_status mec_encode_frames_batch_var(mec_ctx *ctx, int n,
+                                       const uint8_t *data,
+                                       const int64_t *block_lens,
+                                       uint8_t *frames, int bitrot_algo);
+
 /* ---- batch reconstruct (ReconstructData / Reconstruct / Heal kernel) ---
  *
  * shards_dev: n * (d+p) * stride bytes; present[i] != 0 marks shard row i

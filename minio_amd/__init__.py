@@ -21,6 +21,12 @@ surfaces 1:1 for tests and benchmarks:
                             objects: Erasure.Encode encodes whatever
                             io.ReadFull returned, cmd/erasure-encode.go:
                             76-108; mec_encode_batch_var)
+  - Erasure.encode_frames_batch_var, frame_offsets
+                        <-> the same batch written as streamingBitrotWriter
+                            writes it: one [hash||shard] frame per block in
+                            each of the d+p row streams
+                            (cmd/bitrot-streaming.go:44-75;
+                             mec_encode_frames_batch_var)
   - Erasure.reconstruct_batch
                         <-> DecodeDataBlocks / DecodeDataAndParityBlocks
                             for many blocks in one call, each with its own
@@ -122,6 +128,11 @@ def _load():
     lib.mec_encode_batch_var.argtypes = [vp, i32, u8p, i64p, u8p, i32, u8p]
     lib.mec_encode_batch_var_dev.argtypes = [vp, i32, vp, i64p, vp, i32, vp]
     lib.mec_encode_batch_var_dev_async.argtypes = [vp, i32, vp, i64p, vp, i32, vp]
+    lib.mec_frame_offsets.argtypes = [i32, i64, i32, i64p, i64p]
+    lib.mec_encode_frames_batch_var.argtypes = [vp, i32, u8p, i64p, u8p, i32]
+    lib.mec_encode_frames_batch_var_dev.argtypes = [vp, i32, vp, i64p, vp, i32]
+    lib.mec_encode_frames_batch_var_dev_async.argtypes = [
+        vp, i32, vp, i64p, vp, i32]
     lib.mec_reconstruct_batch.argtypes = [vp, i32, u8p, u8p, i64, i32]
     lib.mec_reconstruct_batch_dev.argtypes = [vp, i32, vp, u8p, i64, i32]
     lib.mec_reconstruct_batch_dev_async.argtypes = [vp, i32, vp, u8p, i64, i32]
@@ -209,6 +220,19 @@ def var_row_offsets(d: int, block_size: int, lens) -> list:
     arr = (ctypes.c_int64 * max(n, 1))(*lens)
     out = (ctypes.c_int64 * (n + 1))()
     _check(_lib.mec_var_row_offsets(d, block_size, n, arr, out))
+    return list(out)
+
+
+def frame_offsets(d: int, block_size: int, lens) -> list:
+    """Frame offsets F_0..F_n of the batch encode into on-disk frames
+    (mec_frame_offsets): F_{i+1} = F_i + 32 + ceil(lens[i]/d).  Item i's
+    [hash||shard] frame starts at F_i of every row stream, and a row stream
+    is F_n bytes.  Raises MecError(6) for an empty list or a length outside
+    [1, block_size]."""
+    n = len(lens)
+    arr = (ctypes.c_int64 * max(n, 1))(*lens)
+    out = (ctypes.c_int64 * (n + 1))()
+    _check(_lib.mec_frame_offsets(d, block_size, n, arr, out))
     return list(out)
 
 
@@ -351,6 +375,34 @@ class Erasure:
                 sums.append([sraw[(b * t + s) * 32:(b * t + s + 1) * 32]
                              for s in range(t)])
         return out, sums
+
+    def encode_frames_batch_var(self, blocks, algo: int = None):
+        """encode_batch_var straight into the on-disk format
+        (mec_encode_frames_batch_var): every block becomes one
+        [hash||shard] frame of streamingBitrotWriter
+        (cmd/bitrot-streaming.go:44-75) in each of the d+p row streams.
+
+        blocks: list of bytes, each of its own length in [1, block_size].
+        Returns (streams, offsets): streams[s] is row s's byte stream, in
+        which block i's frame is [offsets[i], offsets[i+1]); consecutive
+        blocks of one object make that object's shard file.  algo defaults
+        to HIGHWAYHASH256S and must be it or HIGHWAYHASH256."""
+        n = len(blocks)
+        t = self.d + self.p
+        if n == 0:
+            return [b""] * t, [0]
+        if algo is None:
+            algo = HIGHWAYHASH256S
+        lens = [len(b) for b in blocks]
+        # the library refuses the lengths itself; without offsets there is
+        # no buffer to hand it
+        off = frame_offsets(self.d, self.block_size, lens)
+        buf = ctypes.create_string_buffer(t * off[-1])
+        _check(_lib.mec_encode_frames_batch_var(
+            self._ck(), n, b"".join(blocks), (ctypes.c_int64 * n)(*lens),
+            buf, algo))
+        raw = buf.raw
+        return [raw[s * off[-1]:(s + 1) * off[-1]] for s in range(t)], off
 
     # -- DecodeDataBlocks / DecodeDataAndParityBlocks --
     def decode_data_blocks(self, shards):

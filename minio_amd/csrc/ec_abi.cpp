@@ -13,6 +13,7 @@
  * (MEC_ERR_NO_GPU / MEC_ERR_HIP).
  */
 #include "../../include/minio_ec.h"
+#include "frames_plan.h"
 #include "gf_host.h"
 #include "kernels.h"
 #include "read_var_plan.h"
@@ -143,6 +144,13 @@ struct mec_ctx {
     hipEvent_t ev_e[2] = {nullptr, nullptr};
     int e_idx = 0;
     mec::VarPlan vplan; /* reused across calls to keep its allocations */
+    /* encode into frames: the F prefix rides in dev_e behind the encode's
+     * tables; dev_f holds the call's parity rows and, behind them, its sums
+     * table.  Grow-only, rewritten only behind the kernels that read it, by
+     * stream order. */
+    mec::FramesPlan fplan;
+    void *dev_f = nullptr;
+    size_t cap_f = 0;
     /* per-item-length verified read: tile prefixes of the call's work
      * lists, and the host offsets of the packed rows (host-pointer call) */
     std::vector<int64_t> vtiles[MEC_KMAX_E + 1];
@@ -291,6 +299,7 @@ void mec_ctx_destroy(mec_ctx *ctx) {
     if (ctx->dev_v) (void)hipFree(ctx->dev_v);
     if (ctx->pin_v) (void)hipHostFree(ctx->pin_v);
     if (ctx->dev_e) (void)hipFree(ctx->dev_e);
+    if (ctx->dev_f) (void)hipFree(ctx->dev_f);
     for (int s = 0; s < 2; s++) {
         if (ctx->pin_e[s]) (void)hipHostFree(ctx->pin_e[s]);
         if (ctx->ev_e[s]) (void)hipEventDestroy(ctx->ev_e[s]);
@@ -646,6 +655,16 @@ mec_status mec_var_row_offsets(int d, int64_t block_size, int n,
     return MEC_OK;
 }
 
+/* MEC_ERR_INVALID_ARG, with the message, for a geometry that has no compiled
+ * gf_encode_bs_var_kernel */
+static mec_status var_geometry_check(const mec_ctx *ctx) {
+    if (mec_encode_var_supported(ctx->d, ctx->p)) return MEC_OK;
+    g_last_error = "per-item-length encode needs a compiled (d,p) "
+                   "specialization; EC" + std::to_string(ctx->d) + "+" +
+                   std::to_string(ctx->p) + " has none";
+    return MEC_ERR_INVALID_ARG;
+}
+
 /* Everything that can be refused is refused here, before anything is
  * launched or written; on MEC_OK ctx->vplan holds the call's plan. */
 static mec_status var_check_locked(mec_ctx *ctx, int n, const void *data,
@@ -658,23 +677,46 @@ static mec_status var_check_locked(mec_ctx *ctx, int n, const void *data,
     if (sums && algo != MEC_BITROT_HIGHWAYHASH256S &&
         algo != MEC_BITROT_HIGHWAYHASH256)
         return MEC_ERR_INVALID_ARG;
-    if (!mec_encode_var_supported(ctx->d, ctx->p)) {
-        g_last_error = "per-item-length encode needs a compiled (d,p) "
-                       "specialization; EC" + std::to_string(ctx->d) + "+" +
-                       std::to_string(ctx->p) + " has none";
-        return MEC_ERR_INVALID_ARG;
-    }
+    if (var_geometry_check(ctx) != MEC_OK) return MEC_ERR_INVALID_ARG;
     if (!mec::build_var_plan(ctx->d, ctx->d + ctx->p, ctx->block_size, n,
                              block_lens, &ctx->vplan))
         return MEC_ERR_INVALID_ARG;
     return MEC_OK;
 }
 
+/* Split scatter (cmd/erasure-coding.go:81) of each block of the
+ * concatenated `data` into its own rows of the packed layout at pinb: shard
+ * k gets bytes [k*S_i, (k+1)*S_i), zero-padded to S_i. */
+static void var_scatter_host(const mec::VarPlan &pl, int d,
+                             const uint8_t *data, const int64_t *block_lens,
+                             uint8_t *pinb) {
+    const uint8_t *blk = data;
+    const size_t n = pl.items.size();
+    for (size_t b = 0; b < n; b++) {
+        const int64_t S = pl.items[b].shard_len;
+        const int64_t stride = (S + 63) & ~int64_t(63);
+        uint8_t *rows = pinb + (size_t)d * pl.items[b].row_off;
+        for (int k = 0; k < d; k++) {
+            uint8_t *dst = rows + (size_t)k * stride;
+            int64_t have = block_lens[b] - (int64_t)k * S;
+            if (have < 0) have = 0;
+            if (have > S) have = S;
+            if (have) memcpy(dst, blk + (int64_t)k * S, (size_t)have);
+            if (have < S) memset(dst + have, 0, (size_t)(S - have));
+        }
+        blk += block_lens[b];
+    }
+}
+
 /* Uploads ctx->vplan's tables and launches the two kernels.  Never
  * synchronizes the stream; the only host wait is on the copy that last
  * read the pinned slot being refilled (two calls back). */
+/* extra, when given, is one more table of the call (the frames path's F
+ * prefix): it rides in the same upload, and *extra_dev is where it lands. */
 static mec_status var_launch_locked(mec_ctx *ctx, const void *data_dev,
-                                    void *parity_dev, void *sums_dev) {
+                                    void *parity_dev, void *sums_dev,
+                                    const std::vector<int64_t> *extra = nullptr,
+                                    const int64_t **extra_dev = nullptr) {
     const mec::VarPlan &pl = ctx->vplan;
     const size_t n = pl.items.size();
     auto al16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
@@ -682,7 +724,9 @@ static mec_status var_launch_locked(mec_ctx *ctx, const void *data_dev,
     const size_t col_off = al16(item_bytes);
     const size_t col_bytes = (n + 1) * sizeof(int64_t);
     const size_t ord_off = al16(col_off + col_bytes);
-    const size_t end = al16(ord_off + n * sizeof(uint32_t));
+    const size_t ext_off = al16(ord_off + n * sizeof(uint32_t));
+    const size_t ext_bytes = extra ? extra->size() * sizeof(int64_t) : 0;
+    const size_t end = al16(ext_off + ext_bytes);
 
     const int slot = ctx->e_idx & 1;
     ctx->e_idx ^= 1;
@@ -708,11 +752,13 @@ static mec_status var_launch_locked(mec_ctx *ctx, const void *data_dev,
     memcpy(pinb, pl.items.data(), item_bytes);
     memcpy(pinb + col_off, pl.col_off.data(), col_bytes);
     memcpy(pinb + ord_off, pl.order.data(), n * sizeof(uint32_t));
+    if (extra) memcpy(pinb + ext_off, extra->data(), ext_bytes);
     HIP_TRY(hipMemcpyAsync(ctx->dev_e, pinb, end, hipMemcpyHostToDevice,
                            ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev_e[slot], ctx->stream));
 
     const uint8_t *de = (const uint8_t *)ctx->dev_e;
+    if (extra_dev) *extra_dev = (const int64_t *)(de + ext_off);
     EncVarArgs a{};
     a.data = (const uint8_t *)data_dev;
     a.parity = (uint8_t *)parity_dev;
@@ -789,25 +835,10 @@ mec_status mec_encode_batch_var(mec_ctx *ctx, int n, const uint8_t *data,
                                   : par_bytes + sum_bytes)) != MEC_OK)
         return st;
 
-    /* Split scatter (cmd/erasure-coding.go:81) of each block into its own
-     * rows: shard k gets bytes [k*S_i, (k+1)*S_i), zero-padded to S_i.
-     * Plain unchunked upload, as mec_reconstruct_batch_mixed. */
+    /* Split scatter into pinned staging, then a plain unchunked upload, as
+     * mec_reconstruct_batch_mixed. */
     uint8_t *pinb = (uint8_t *)ctx->pin;
-    const uint8_t *blk = data;
-    for (int b = 0; b < n; b++) {
-        const int64_t S = pl.items[(size_t)b].shard_len;
-        const int64_t stride = (S + 63) & ~int64_t(63);
-        uint8_t *rows = pinb + (size_t)d * pl.items[(size_t)b].row_off;
-        for (int k = 0; k < d; k++) {
-            uint8_t *dst = rows + (size_t)k * stride;
-            int64_t have = block_lens[b] - (int64_t)k * S;
-            if (have < 0) have = 0;
-            if (have > S) have = S;
-            if (have) memcpy(dst, blk + (int64_t)k * S, (size_t)have);
-            if (have < S) memset(dst + have, 0, (size_t)(S - have));
-        }
-        blk += block_lens[b];
-    }
+    var_scatter_host(pl, d, data, block_lens, pinb);
     HIP_TRY(hipMemcpyAsync(ctx->dev_a, pinb, data_bytes, hipMemcpyHostToDevice,
                            ctx->stream));
     st = var_launch_locked(ctx, ctx->dev_a, ctx->dev_b,
@@ -829,6 +860,143 @@ mec_status mec_encode_batch_var(mec_ctx *ctx, int n, const uint8_t *data,
             memcpy(out, rows + (size_t)t * stride, (size_t)S);
     }
     if (sums) memcpy(sums, pinb + par_bytes, sum_bytes);
+    return MEC_OK;
+}
+
+/* ---- batch encode into on-disk [hash||shard] frames, length PER ITEM ---- */
+
+mec_status mec_frame_offsets(int d, int64_t block_size, int n,
+                             const int64_t *block_lens, int64_t *frame_off) {
+    return mec::frame_offsets(d, block_size, n, block_lens, frame_off)
+               ? MEC_OK
+               : MEC_ERR_INVALID_ARG;
+}
+
+/* Everything that can be refused is refused here, before anything is
+ * launched or written; on MEC_OK ctx->vplan and ctx->fplan hold the call's
+ * plan. */
+static mec_status frames_check_locked(mec_ctx *ctx, int n, const void *data,
+                                      const int64_t *block_lens,
+                                      const void *frames, int algo) {
+    if (n <= 0 || !data || !block_lens || !frames) return MEC_ERR_INVALID_ARG;
+    /* a frame's digest is HighwayHash-256 with the magic key; both ids name
+     * that function */
+    if (algo != MEC_BITROT_HIGHWAYHASH256S && algo != MEC_BITROT_HIGHWAYHASH256)
+        return MEC_ERR_INVALID_ARG;
+    if (var_geometry_check(ctx) != MEC_OK) return MEC_ERR_INVALID_ARG;
+    if (!mec::build_frames_plan(ctx->d, ctx->d + ctx->p, ctx->block_size, n,
+                                block_lens, &ctx->vplan, &ctx->fplan))
+        return MEC_ERR_INVALID_ARG;
+    return MEC_OK;
+}
+
+/* The encode's two launches into context scratch, then the pack.  Never
+ * synchronizes the stream (but see var_launch_locked on the pinned slots). */
+static mec_status frames_launch_locked(mec_ctx *ctx, const void *data_dev,
+                                       void *frames_dev) {
+    const mec::VarPlan &pl = ctx->vplan;
+    const int d = ctx->d, p = ctx->p;
+    const size_t n = pl.items.size();
+    /* R_n is a multiple of 64, so the sums table starts aligned */
+    const size_t par_bytes = (size_t)p * pl.rows_total;
+    const size_t need = par_bytes + n * (size_t)(d + p) * 32;
+    /* growing dev_f frees the old buffer, which waits for the kernels
+     * still using it; grow with a quarter of slack so that stays rare (the
+     * buffer is p/d of the input, so not doubled as the tables are) */
+    if (ctx->cap_f < need) {
+        mec_status st =
+            ctx->ensure(&ctx->dev_f, &ctx->cap_f, need + need / 4);
+        if (st != MEC_OK) return st;
+    }
+    uint8_t *parity = (uint8_t *)ctx->dev_f;
+    uint8_t *sums = parity + par_bytes;
+    const int64_t *f_dev = nullptr;
+    mec_status st = var_launch_locked(ctx, data_dev, parity, sums,
+                                      &ctx->fplan.frame_off, &f_dev);
+    if (st != MEC_OK) return st;
+
+    FramesPackArgs a{};
+    a.data = (const uint8_t *)data_dev;
+    a.parity = parity;
+    a.sums = sums;
+    a.out = (uint8_t *)frames_dev;
+    a.items = (const int64_t *)ctx->dev_e;
+    a.frame_off = f_dev;
+    a.fn = ctx->fplan.frame_off[n];
+    a.bytes = ctx->fplan.frames_bytes;
+    a.a0 = (uint32_t)((uintptr_t)frames_dev & 15);
+    a.granules = ((int64_t)a.a0 + a.bytes + 15) >> 4;
+    a.n = (uint32_t)n;
+    a.d = d;
+    a.p = p;
+    hipError_t he = mec_launch_frames_pack(&a, ctx->stream);
+    if (he != hipSuccess) {
+        set_err("frames_pack", he);
+        return MEC_ERR_HIP;
+    }
+    return MEC_OK;
+}
+
+mec_status mec_encode_frames_batch_var_dev_async(mec_ctx *ctx, int n,
+                                                 const void *data_dev,
+                                                 const int64_t *block_lens,
+                                                 void *frames_dev,
+                                                 int bitrot_algo) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mec_status st = frames_check_locked(ctx, n, data_dev, block_lens,
+                                        frames_dev, bitrot_algo);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return frames_launch_locked(ctx, data_dev, frames_dev);
+}
+
+mec_status mec_encode_frames_batch_var_dev(mec_ctx *ctx, int n,
+                                           const void *data_dev,
+                                           const int64_t *block_lens,
+                                           void *frames_dev,
+                                           int bitrot_algo) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mec_status st = frames_check_locked(ctx, n, data_dev, block_lens,
+                                        frames_dev, bitrot_algo);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipSetDevice(ctx->device));
+    st = frames_launch_locked(ctx, data_dev, frames_dev);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MEC_OK;
+}
+
+mec_status mec_encode_frames_batch_var(mec_ctx *ctx, int n,
+                                       const uint8_t *data,
+                                       const int64_t *block_lens,
+                                       uint8_t *frames, int bitrot_algo) {
+    if (!ctx) return MEC_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mec_status st =
+        frames_check_locked(ctx, n, data, block_lens, frames, bitrot_algo);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const mec::VarPlan &pl = ctx->vplan;
+    const size_t data_bytes = (size_t)ctx->d * pl.rows_total;
+    const size_t out_bytes = (size_t)ctx->fplan.frames_bytes;
+    if ((st = ctx->ensure(&ctx->dev_a, &ctx->cap_a, data_bytes)) != MEC_OK)
+        return st;
+    if ((st = ctx->ensure(&ctx->dev_d, &ctx->cap_d, out_bytes)) != MEC_OK)
+        return st;
+    if ((st = ctx->ensure_pin(data_bytes)) != MEC_OK) return st;
+    /* Split scatter into pinned staging, one plain upload (no overlapped
+     * ingest), the device path, one D2H of every row stream */
+    uint8_t *pinb = (uint8_t *)ctx->pin;
+    var_scatter_host(pl, ctx->d, data, block_lens, pinb);
+    HIP_TRY(hipMemcpyAsync(ctx->dev_a, pinb, data_bytes, hipMemcpyHostToDevice,
+                           ctx->stream));
+    st = frames_launch_locked(ctx, ctx->dev_a, ctx->dev_d);
+    if (st != MEC_OK) return st;
+    HIP_TRY(hipMemcpyAsync(frames, ctx->dev_d, out_bytes,
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return MEC_OK;
 }
 

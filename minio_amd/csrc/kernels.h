@@ -147,6 +147,27 @@ struct EncVarArgs {
     uint64_t key[4];
 };
 
+/* Pack rows and digests into on-disk [hash||shard] frames
+ * (encode_frames.hip).  Input: EncVarArgs' data, parity and sums after
+ * mec_launch_encode_var.  Output layout: frames_plan.h; the mapping from an
+ * output granule to its source: frames_map.h. */
+struct FramesPackArgs {
+    const uint8_t *data;      /* d * R_n, 16-aligned */
+    const uint8_t *parity;    /* p * R_n, 16-aligned */
+    const uint8_t *sums;      /* n * (d+p) * 32 */
+    uint8_t *out;             /* (d+p) * F_n bytes, any alignment */
+    const int64_t *items;     /* 2 per item: R_i, S_i (mec::VarItem) */
+    const int64_t *frame_off; /* n+1: F_0..F_n */
+    int64_t fn;               /* F_n */
+    int64_t bytes;            /* (d+p) * F_n */
+    int64_t granules;         /* ceil((a0 + bytes) / 16) */
+    int64_t groups;           /* ceil(granules / 64); the launcher fills it */
+    int64_t per_wave;         /* consecutive groups per wave; the launcher's */
+    uint32_t n;
+    uint32_t a0;              /* out address % 16 */
+    int d, p;
+};
+
 /* Fused single-pass encode+HighwayHash (fused4.hip) */
 struct FusedArgs {
     const uint8_t *data; /* n * d * row_stride */
@@ -207,6 +228,9 @@ int mec_encode_var_supported(int d, int p);
 /* gf_encode_bs_var_kernel, then hh256_var_kernel unless args->sums is NULL;
  * hipErrorNotSupported, with nothing launched, for an unspecialized (d,p) */
 hipError_t mec_launch_encode_var(const EncVarArgs *args, hipStream_t stream);
+/* frames_pack_var_kernel over args->granules output granules */
+hipError_t mec_launch_frames_pack(const FramesPackArgs *args,
+                                  hipStream_t stream);
 hipError_t mec_launch_hash(int algo, const HashArgs *args, hipStream_t stream);
 /* HighwayHash-256 over args->list; verify != 0 selects hh256_list_verify,
  * else hh256_list_sum.  n_list == 0 launches nothing. */
